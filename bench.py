@@ -15,6 +15,12 @@ every fp32 product as three fp16 MFMA products); the fp16-operand mode is an ext
 
     python bench.py [--gpus N --steps K --warmup W]      (N > 1: launches N ranks itself)
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline rate,
+`ms_per_step`, per-stage HIP-event times of the timed frames).  `--dump-outputs DIR` also writes what the
+last timed step returned as DIR/<name>.npy.  `--full` adds everything else to the line: roofline and
+occupancy figures (an untimed re-render of the timed frames), the grid rebuild time, the other arithmetic
+mode, the training, dense-stress, lego, SG and config-3 extras, and the CPU baseline.
 """
 import argparse
 import gc
@@ -61,7 +67,13 @@ def parse():
     ap.add_argument("--points", type=int, default=None, help="neural points (default 1.2M room, 300k lego)")
     ap.add_argument("--scene", choices=["room", "lego", "dense", "spiral"], default="room",
                     help="room: BASELINE config 2 (headline); lego: config 4 (NeRF-synthetic camera, SR 128)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / occupancy figures, grid rebuild, "
+                         "the extra keys (--no-extras drops them) and the CPU baseline (--no-cpu-baseline drops it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy "
+                         "(float32; a fixed seeded row sample of an output too large for the 64 MB total)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
     ap.add_argument("--train", action="store_true",
@@ -76,8 +88,31 @@ def parse():
     ap.add_argument("--precision", choices=["f32", "f16"], default="f32",
                     help="aggregator arithmetic of the headline (f32: the reference's; f16: fp16 MFMA operands)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra keys (f16-mode frame rate, config-5 training rate)")
+                    help="with --full: skip the extra keys (f16-mode frame rate, config-5 training rate, ...)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 60_000_000   # all of --dump-outputs' files together stay under 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` (name -> device tensor, what a caller of the timed path received from its last
+    step) as dirname/<name>.npy in float32.  Small arrays are written whole; one whose share of DUMP_BYTES is
+    too small is cut to a fixed sample of its rows (generator seeded with 0, rows in ascending order), the
+    same rows in every run of the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BYTES
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for j, (name, t) in enumerate(todo):
+        t = t.detach()
+        share = left // (len(todo) - j)
+        row_bytes = 4 * max(t.numel() // max(t.shape[0], 1), 1) if t.dim() else 4
+        if t.dim() and t.numel() * 4 > share:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=max(share // row_bytes, 1), replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = np.ascontiguousarray(t.to(torch.float32).cpu().numpy())
+        left -= a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def self_launch(args):
@@ -87,7 +122,7 @@ def self_launch(args):
     return sd.launch_ranks(__file__, args.gpus, sys.argv[1:]).returncode
 
 
-def train_main(args, world, rank, dev, dist, steps=None, warmup=None, precision=None):
+def train_main(args, world, rank, dev, dist, steps=None, warmup=None, precision=None, dump_dir=None):
     """Config 5: one training step = 4096 random rays of a random spiral pose per rank, HIP query,
     device autograd through aggregator + composite, bucketed RCCL all-reduce, two Adam groups.
     Returns the result dict (rank 0 prints it when run as the headline)."""
@@ -135,7 +170,7 @@ def train_main(args, world, rank, dev, dist, steps=None, warmup=None, precision=
     losses = []
     for i in range(warmup, n_steps):
         c, r_, d, gt = batches[i]
-        parts, _, _ = tr.step(c, r_, d, 0.1, 8.0, gt, **_lab(labels[i]))
+        parts, rgb, ray_mask = tr.step(c, r_, d, 0.1, 8.0, gt, **_lab(labels[i]))
         losses.append(parts["total"])
     torch.cuda.synchronize()
     if dist:
@@ -144,6 +179,8 @@ def train_main(args, world, rank, dev, dist, steps=None, warmup=None, precision=
     if dist:
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(el.item())
+    if dump_dir and rank == 0 and steps > 0:   # the last timed step's return values (untimed)
+        dump_outputs(dump_dir, {"loss_total": parts["total"], "rgb": rgb, "ray_mask": ray_mask})
     rays = args.train_rays * steps * world
     res = {"metric": "training rays/sec, 4096-ray batches with backward, DP (BASELINE config 5)",
            "value": rays / elapsed, "unit": "rays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
@@ -280,8 +317,9 @@ def dense_pose_view(i, h, w):
     return scene.dense_stress_view(h, w, shift=0.02 * ((i % 5) - 2))
 
 
-def render_run(args, precision, world, rank, dev, dist, steps, warmup, lego, want_stats=True):
-    """Headline-shaped frame loop at `precision`; returns the result fields (no cpu baseline)."""
+def render_run(args, precision, world, rank, dev, dist, steps, warmup, lego, want_stats=True, dump_dir=None):
+    """Headline-shaped frame loop at `precision`; returns the result fields (no cpu baseline).  `dump_dir`:
+    rank 0 writes the last timed frame's outputs there (dump_outputs), after the clock has stopped."""
     sg = dict(shading_feature_mlp_layer2_bpnet=1, predict_semantic=1, semantic_guidance=1) if args.sg else {}
     o = HotPathOpts(SR=args.sr, precision=precision, **sg)
     dense = args.scene == "dense"
@@ -379,7 +417,7 @@ def render_run(args, precision, world, rank, dev, dist, steps, warmup, lego, wan
     t0 = time.perf_counter()
     for i in range(warmup, n_frames):
         events.append({})
-        frame(i, marks)
+        out = frame(i, marks)
     drain()
     torch.cuda.synchronize()
     if dist:
@@ -389,6 +427,9 @@ def render_run(args, precision, world, rank, dev, dist, steps, warmup, lego, wan
     if dist:
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(el.item())
+    if dump_dir and rank == 0 and steps > 0:
+        dump_outputs(dump_dir, {"rgb": out.rgb, "ray_mask": out.ray_mask, "bg_transmission": out.bg_transmission,
+                                "coarse_point_opacity": out.opacity})
     stage_names = ["query", "proj", "agg_rows", "agg_color", "composite"]
     order = stage_names + ["end"]
     stage_ms = {n: float(np.mean([ev[n].elapsed_time(ev[order[j + 1]]) for ev in events]))
@@ -508,30 +549,17 @@ def main():
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
     if args.train:
-        res = train_main(args, world, rank, dev, dist)
+        res = train_main(args, world, rank, dev, dist, dump_dir=args.dump_outputs)
         if rank == 0:
             print(json.dumps(res))
         if dist:
             torch.distributed.destroy_process_group()
         return
     x3 = args.precision == "f32"
-    h = render_run(args, args.precision, world, rank, dev, dist, args.steps, args.warmup, lego)
+    # a plain run stops after the timed frames; --full re-renders them untimed for the occupancy / roofline figures
+    h = render_run(args, args.precision, world, rank, dev, dist, args.steps, args.warmup, lego, want_stats=args.full,
+                   dump_dir=args.dump_outputs)
     R = args.h * args.w
-    stage_ms = h["stages_ms"]
-    flop_nb = FLOP_PER_ROW_SPLIT + (2 * 352 * 256 if args.sg else 0)  # + block2_bpnet.0 (SG)
-    rows_flop = flop_nb * h["n_nb"]
-    ref_flop = (FLOP_PER_NB + (2 * 352 * 256 if args.sg else 0)) * h["n_nb"]
-    achieved = rows_flop / (stage_ms["agg_rows"] * 1e-3) / 1e12
-    peak = PEAK_X3_TFLOPS if x3 else PEAK_F16_TFLOPS
-    kname = "k_rows16" if x3 else "k_agg_rows"
-    traffic = None
-    if os.path.exists(args.traffic_json):
-        try:
-            tj = json.load(open(args.traffic_json))
-            if tj.get("kernel") == kname and tj.get("workload_key") == f"{args.h}x{args.w}x{args.sr}":
-                traffic = tj.get("bytes_per_launch")
-        except Exception:
-            traffic = None
     res = {
         "metric": METRIC,
         "value": h["value"],
@@ -558,6 +586,40 @@ def main():
             "mlp": "viewmlp 284-256-256 / 263-256-256 / alpha / colour 280-128x3-3 (341,764 params, random init)",
             "outputs": "rgb, ray mask, background transmission, coarse_point_opacity [R, SR]",
         },
+        "stages_ms": h["stages_ms"],
+        "grid_build_ms": h["grid_build_ms"],
+        "ms_per_frame": h["ms_per_frame"],
+    }
+    if args.full:
+        full_figures(args, res, h, world, rank, dev, dist, lego)
+    if rank == 0:
+        print(json.dumps(res))
+    if dist:
+        torch.distributed.destroy_process_group()
+
+
+def full_figures(args, res, h, world, rank, dev, dist, lego):
+    """--full: what the headline figure does not need, added to the result line `res` of the headline run `h`
+    (render_run with want_stats): roofline and occupancy figures, the grid rebuild time, the extra
+    workloads (each a run of its own; --no-extras drops them) and the CPU baseline (--no-cpu-baseline)."""
+    x3 = args.precision == "f32"
+    R = args.h * args.w
+    stage_ms = h["stages_ms"]
+    flop_nb =FLOP_PER_ROW_SPLIT + (2 * 352 * 256 if args.sg else 0)  # + block2_bpnet.0 (SG)
+    rows_flop = flop_nb * h["n_nb"]
+    ref_flop = (FLOP_PER_NB + (2 * 352 * 256 if args.sg else 0)) * h["n_nb"]
+    achieved = rows_flop / (stage_ms["agg_rows"] * 1e-3) / 1e12
+    peak = PEAK_X3_TFLOPS if x3 else PEAK_F16_TFLOPS
+    kname = "k_rows16" if x3 else "k_agg_rows"
+    traffic = None
+    if os.path.exists(args.traffic_json):
+        try:
+            tj = json.load(open(args.traffic_json))
+            if tj.get("kernel") == kname and tj.get("workload_key") == f"{args.h}x{args.w}x{args.sr}":
+                traffic = tj.get("bytes_per_launch")
+        except Exception:
+            traffic = None
+    res.update({
         "roofline": {
             "kernel": kname + " (per-neighbour MLP 284->256->256->" + ("352->256->" if args.sg else "")
                       + "263->256->256 + alpha + K-blend)",
@@ -588,16 +650,13 @@ def main():
             "bound": "mfma", "achieved": FLOP_PER_POINT_PROJ * h["n_proj"] / (stage_ms["proj"] * 1e-3) / 1e12,
             "peak": peak, "unit": "TFLOP/s", "avg_launch_ms": stage_ms["proj"], "points_projected": h["n_proj"],
         },
-        "stages_ms": stage_ms,
-        "grid_build_ms": h["grid_build_ms"],
         "grid_rebuild_ms": h["grid_rebuild_ms"],
         "occupancy": {
             "samples_per_ray": h["n_samples"] / R,
             "valid_samples_per_ray": h["n_smp"] / R,
             "valid_neighbours_per_ray": h["n_nb"] / R,
         },
-        "ms_per_frame": h["ms_per_frame"],
-    }
+    })
     if not args.no_extras:
         # the other arithmetic mode on the same frames (extra key; the headline stays the reference's fp32)
         other = "f16" if x3 else "f32"
@@ -648,10 +707,6 @@ def main():
             res["train_config5_f16"] = {k: tr16[k] for k in keys}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(h["pc"], h["mlp"], h["o"], h["views"][0])
-    if rank == 0:
-        print(json.dumps(res))
-    if dist:
-        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -2,9 +2,9 @@
 # PMC passes (one rocprofv3 run per counter group, no tracing domains mixed in) for the
 # dominant kernels of bench.py.  Usage (on the GPU box):  bash tools/profile_pmc.sh <outdir> [bench args]
 set -e
-OUT=${1:-gpurun_out/pmc}
+OUT=${1:-${SGN_OUT:-bench_out}/pmc}
 shift || true
-ARGS=${@:---steps 2 --warmup 1 --no-cpu-baseline --no-extras}
+ARGS=${@:---full --steps 2 --warmup 1 --no-cpu-baseline --no-extras}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 i=0
