@@ -1,4 +1,9 @@
-"""Training step of the per-ray path, first version.
+"""The torch-autograd reference trainer and the data-parallel helpers.
+
+`Trainer` is the fp32 restatement of the training step that the parity tests and
+`bench.py --train-torch` compare the HIP step (train_hip.HipTrainer) against; `PointParams`,
+`_allreduce_buckets`, `touched_rows`, `gather_counts` and `_allreduce_point_rows` are what
+HipTrainer imports from here.
 
 One step on a batch of rays, as the reference's `optimize_parameters` does it
 (models/base_rendering_model.py:534-664, models/mvs_points_volumetric_model.py:47-141):
@@ -20,10 +25,8 @@ One step on a batch of rays, as the reference's `optimize_parameters` does it
                (net lr 5e-4, points plr 2e-3, betas (0.9, 0.999)) with the reference's
                iter_exponential_decay schedule (lr * 0.1 ** (step / 1e6))
 
-The forward used for rendering stays the fused HIP kernels; this module is the
-differentiable restatement needed for gradients until the HIP backward lands.  `loss_from_query`
-takes a query result (sample-major) so the same code runs on CPU with the oracle's query in
-the parity tests.
+`loss_from_query` takes a query result (sample-major) so the same code runs on CPU with the
+oracle's query in the parity tests.
 """
 import math
 import os
@@ -97,22 +100,6 @@ def _w2pers(p, rot, campos):
     return torch.stack([c[..., 0] / c[..., 2], c[..., 1] / c[..., 2], c[..., 2]], dim=-1)
 
 
-class _SavedLinear(torch.autograd.Function):
-    """z = x W^T + b whose forward value was computed elsewhere (the HIP fp32-faithful row kernel,
-    k_rows16's save mode) and is passed in; the backward is the plain fp32 one: dx = dz W,
-    dW = dz^T x, db = sum dz."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, z):
-        ctx.save_for_backward(x, w)
-        return z.clone()
-
-    @staticmethod
-    def backward(ctx, gz):
-        x, w = ctx.saved_tensors
-        return gz @ w, _dw_rows(gz, x), gz.sum(0), None
-
-
 DW_CHUNK_F32 = int(os.environ.get("SGN_DW_CHUNK_F32", "4096"))  # rows per split-K batch (0: one plain GEMM)
 
 
@@ -130,34 +117,8 @@ class _LinearRows(torch.autograd.Function):
         return gz @ w, _dw_rows(gz, x), gz.sum(0)
 
 
-class _LinearSink(torch.autograd.Function):
-    """z = x W^T + b (or the z computed elsewhere, passed in a one-element list) whose weight and
-    bias gradients the backward hands to `sink(gz, x)` -- which adds them into the trainer's flat
-    gradient -- instead of returning them through autograd (autograd through views of a flat
-    parameter zero-fills a full-size gradient per view, copies the slice in and adds it)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, sink, zbox):
-        ctx.save_for_backward(x, w)
-        ctx.sink = sink
-        return zbox[0] if zbox is not None else F.linear(x, w, b)
-
-    @staticmethod
-    def backward(ctx, gz):
-        x, w = ctx.saved_tensors
-        gz = gz.contiguous()
-        ctx.sink(gz, x)
-        return (gz @ w if ctx.needs_input_grad[0] else None), None, None, None, None
-
-
-def _linear(mlp, name, x, z=None, split=False):
-    """One aggregator layer: through the mlp's gradient sink when it has one (the HIP trainer's flat
-    parameter), else _SavedLinear (z given) / _LinearRows (split-K dW) / nn.Linear."""
-    sink = mlp.grad_sink(name) if hasattr(mlp, "grad_sink") else None
-    if sink is not None:
-        return _LinearSink.apply(x, mlp.w(name).detach(), mlp.b(name).detach(), sink, None if z is None else [z])
-    if z is not None:
-        return _SavedLinear.apply(x, mlp.w(name), mlp.b(name), z)
+def _linear(mlp, name, x, split=False):
+    """One aggregator layer: _LinearRows (split-K dW) or nn.Linear."""
     if split:
         return _LinearRows.apply(x, mlp.w(name), mlp.b(name))
     return mlp.f(name, x)
@@ -179,20 +140,13 @@ def _dw_rows(gz, x, chunk=DW_CHUNK_F32):
     return g
 
 
-def aggregate(points: PointParams, mlp: ViewMLP, campos, rot, raydir, samp_ray, samp_locw, pidx, saved=None,
-              rows=None):
+def aggregate(points: PointParams, mlp: ViewMLP, campos, rot, raydir, samp_ray, samp_locw, pidx):
     """Differentiable PointAggregator.forward on sample-major neighbours.
     Returns feat [S,4] (alpha, r, g, b; zeros for samples without neighbours), conf_coefficient
     [S,K] (straight-through clamp) and the neighbour mask [S,K].
 
-    saved = (z1, z2, z3): the pre-activations of block1.0, block1.2 and block3.0 per row s * K + k
-    ([>= S K, 256] fp32, from sgn_aggregate_train_fwd_f32): those three layers then take their
-    forward values from there (_SavedLinear) instead of recomputing them, with the same fp32
-    backward.
-
-    rows: the valid rows s * K + k in order (torch.nonzero of pidx >= 0), when the caller has them
-    without a host sync (nonzero_static with a device-side count); else computed here (one sync).
-    Every masked selection goes through them (index_select / index_copy, no further syncs)."""
+    Every masked selection goes through the valid rows s * K + k (torch.nonzero of pidx >= 0: one
+    host sync), by index_select / index_copy (no further syncs)."""
     S, K = pidx.shape
     mask = pidx >= 0
     flat = torch.clamp(pidx, min=0).reshape(-1).long()
@@ -213,22 +167,16 @@ def aggregate(points: PointParams, mlp: ViewMLP, campos, rot, raydir, samp_ray, 
     vpe = _pe(v, 4, ori=True)
     ori_v, vpe = vpe[..., :3], vpe[..., 3:]
     m = mask.reshape(-1)
-    if rows is None:
-        rows = torch.nonzero(m).reshape(-1)   # the valid rows s * K + k, in the order of m
+    rows = torch.nonzero(m).reshape(-1)   # the valid rows s * K + k, in the order of m
     fm = flat.index_select(0, rows)  # index_select: its backward is an index_add (atomics), not a sort-based index_put
     emb = torch.index_select(points.points_embeding, 0, fm)
     x = torch.cat([emb, _pe(emb, 3), _pe(dists.reshape(-1, 6).index_select(0, rows), 5)], dim=-1)
     lr_ = lambda t: F.leaky_relu(t, 0.01)  # noqa: E731
-    if saved is not None:
-        zs = [z.index_select(0, rows) for z in saved]
-        lin = lambda name, t, zi: _linear(mlp, name, t, z=zs[zi])  # noqa: E731
-    else:
-        lin = lambda name, t, zi: _linear(mlp, name, t)  # noqa: E731
-    h = lr_(lin("block1.2", lr_(lin("block1.0", x, 0)), 1))
+    h = lr_(_linear(mlp, "block1.2", lr_(_linear(mlp, "block1.0", x))))
     sd = torch.index_select(points.points_dir, 0, fm)
     ov = ori_v[:, None, :].expand(S, K, 3).reshape(-1, 3).index_select(0, rows)
     h = torch.cat([h, torch.index_select(points.points_color, 0, fm), sd - ov, torch.sum(sd * ov, dim=-1, keepdim=True)], dim=-1)
-    h = lr_(_linear(mlp, "block3.2", lr_(lin("block3.0", h, 2)), split=True))
+    h = lr_(_linear(mlp, "block3.2", lr_(_linear(mlp, "block3.0", h)), split=True))
     alpha = F.softplus(mlp.f("alpha_branch.0", h) - 1)
     hk = torch.zeros(S * K, h.shape[-1], device=h.device, dtype=h.dtype).index_copy(0, rows, h)
     ak = torch.zeros(S * K, 1, device=h.device, dtype=h.dtype).index_copy(0, rows, alpha)

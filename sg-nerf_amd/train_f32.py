@@ -22,6 +22,11 @@ as one captured graph:
 
 Rows r are the valid (sample, neighbour) pairs, sample-major (sample s owns rows
 row_off[s] .. row_off[s] + samp_nnb[s]); items are the samples with a neighbour, ascending.
+
+`ColourStage` is the colour forward, the losses and the colour backward of that sequence; the f16
+step's captured graph (train_f16.F16Step) runs the same stage on its own items.  `F32Runner` is what
+train_hip.HipTrainer drives: it keeps the F32Step of the current batch capacity, the projection
+buffer and the step's touched-point list.
 """
 import ctypes
 import os
@@ -29,6 +34,7 @@ import os
 import torch
 
 from . import _lib
+from .train import gather_counts, touched_rows
 
 # split-K partials of the weight-gradient GEMMs (rows / items cut into this many 32-aligned runs;
 # 84 x 3 column blocks = one workgroup per CU for the row layers).  SGN_SPLITS_ROWS / _ITEMS
@@ -85,13 +91,159 @@ def _attach_bpack(gemms, device):
     return buf
 
 
+class _FlatAddr:
+    """Device addresses inside a trainer's flat parameter, its gradient and the per-layer weight shifts."""
+
+    def __init__(self, trainer):
+        m = self.mlp = trainer.mlp
+        self.flat, self.grad, self.shift = m.flat, m.flat.grad, trainer.packer32.shift
+        self.layer_ix = {name: i for i, (name, *_) in enumerate(m.layers)}
+
+    def W(self, name):
+        off, o, i = self.mlp.slices[name]
+        return _addr(self.flat, off), o, i
+
+    def B(self, name):
+        off, o, i = self.mlp.slices[name]
+        return _addr(self.flat, off + o * i)
+
+    def S(self, name):
+        return _addr(self.shift, self.layer_ix[name])
+
+    def segment(self, part, splits, M, N, name, n_in, bias_col):
+        """A layer's split-K partials [splits, M, N] (its bias gradient in column bias_col) -> flat gradient."""
+        off, o_, i_ = self.mlp.slices[name]
+        s = _lib.PartialSegment()
+        s.part, s.splits, s.M, s.N, s.n_in, s.bias_col, s.ldw = part, splits, M, N, n_in, bias_col, i_
+        s.dst_w, s.dst_b = _addr(self.grad, off), _addr(self.grad, off + o_ * i_)
+        return s
+
+
+class ColourStage:
+    """The colour MLP, the losses and the colour backward of one batch capacity on sgn_x3_gemm, for both
+    precisions (precision "f16" only changes the row MLP).  Items are the samples with a neighbour, `cap`
+    of them at most, their device count at `n_items`.
+
+      forward_and_loss   3 x sgn_x3_gemm forward (3 fp16 products per fp32 product) + sgn_train_colour_head
+                         (rgb into feat[.].yzw), sgn_loss_train (d feat; the zero-one gradients into
+                         points_conf.grad)
+      backward           sgn_train_colour_head_bwd, 2 masked dy W, d f_s = dy1 W0[:, :256], the three weight
+                         gradients as split-K partials
+
+    The owner reduces `segments` (its own after them) into the flat gradient with one sgn_reduce_partials,
+    attaches one bpack workspace to `gemms` and its own, and clears the amax tensor once per step."""
+
+    # amax words (max |x| of a delta tensor, written by its producer, read by its consumers): the first
+    # three of the owner's amax tensor
+    A_DY3, A_DY2, A_DY1 = range(3)
+
+    def __init__(self, trainer, qo, R, cap, n_items, fs, vpe, feat, dfeat, amax, products=3, zero_dfs=False):
+        """n_items: the address of the device item count (int32).  fs [cap, 256] fp32: the items' blended
+        features; vpe [cap, 32]: PE(viewdir) | 1 | 0 (None: allocated here, zeroed); feat [S, 4]: the
+        per-sample features the colour goes into; dfeat: their gradient.  products: of the backward GEMMs,
+        1 (the f16 step's delta precision: one fp16 product per multiply-add) or 3 (split-fp16 at fp32
+        accuracy); the forward keeps 3, so the rendered colour and the losses are the fp32 colour MLP's.
+        zero_dfs: clear d f_s before the backward writes the counted items' rows (padding items then
+        read as 0)."""
+        L = _lib.lib()
+        dev = trainer.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.points, self.qo, self.R = trainer.points, qo, R
+        self.n_items = ctypes.c_void_p(n_items)
+        self.fs, self.feat, self.dfeat, self.amax, self.zero_dfs = fs, feat, dfeat, amax, zero_dfs
+        self.vpe = torch.zeros(cap, 32, **f32) if vpe is None else vpe
+        self.h = [torch.empty(cap, 128, **f32) for _ in range(3)]       # colour h1, h2, h3
+        self.dy = [torch.empty(cap, 128, **f32) for _ in range(3)]      # colour dy1, dy2, dy3
+        self.dfs = torch.empty(cap, 256, **f32)
+        self.losses = torch.zeros(8, **f32)
+        self.full = torch.empty(max(R, 1), 3, **f32)
+        self.mask = torch.empty(max(R, 1), dtype=torch.int8, device=dev)
+        self.loss_ws = torch.empty(max(int(L.sgn_loss_workspace_bytes(R, trainer.opts.SR)), 16), dtype=torch.uint8,
+                                   device=dev)
+        self.part_col = [torch.empty(SPLITS_ITEMS, 128, n, **f32) for n in (129, 129, 281)]
+        self.part_c6 = torch.empty(int(L.sgn_train_head_partial_floats(0)), **f32)
+        # ---- the launch arguments (pointers of persistent buffers: built once) ------------------
+        A = _FlatAddr(trainer)
+        W, S = A.W, A.S
+        am = [_addr(amax, i) for i in range(3)]
+        h1, h2, h3 = (_addr(t) for t in self.h)
+        dy1, dy2, dy3 = (_addr(t) for t in self.dy)
+        fsa, vpa = _addr(fs), _addr(self.vpe)
+        # colour forward: h = LReLU(x W^T + b)
+        w, o_, i_ = W("color_branch.0")
+        G = [_rows_gemm(_operand(fsa, 256, 280, 0, p2=vpa, ld2=32, csplit=256),
+                        _operand(w, i_, i_, 0, shift=S("color_branch.0")), cap, o_, i_, n_items, h1, 128,
+                        bias=A.B("color_branch.0"), act=1)]
+        for name, x, y in (("color_branch.2", h1, h2), ("color_branch.4", h2, h3)):
+            w, o_, i_ = W(name)
+            G.append(_rows_gemm(_operand(x, 128, 128, 0), _operand(w, i_, i_, 0, shift=S(name)), cap, o_, i_, n_items,
+                                y, 128, bias=A.B(name), act=1))
+        self.g_fwd = G
+        # colour backward: dy_prev = (dy W) * LReLU'(h_prev); d f_s = dy1 W0[:, :256]
+        G = []
+        for name, dyi, mk, dyo, ai, ao in (("color_branch.4", dy3, h2, dy2, self.A_DY3, self.A_DY2),
+                                           ("color_branch.2", dy2, h1, dy1, self.A_DY2, self.A_DY1)):
+            w, o_, i_ = W(name)
+            G.append(_rows_gemm(_operand(dyi, 128, 128, 0, amax=am[ai]), _operand(w, i_, i_, 1, shift=S(name)),
+                                cap, i_, o_, n_items, dyo, 128, mask=mk, ldm=128, amax_out=am[ao]))
+        w, o_, i_ = W("color_branch.0")
+        G.append(_rows_gemm(_operand(dy1, 128, 128, 0, amax=am[self.A_DY1]),
+                            _operand(w, i_, 256, 1, shift=S("color_branch.0")), cap, 256, o_, n_items,
+                            _addr(self.dfs), 256))
+        # colour weight gradients (split-K over the items)
+        pc = [_addr(t) for t in self.part_col]
+        G.append(_splitk_gemm(_operand(dy3, 128, 128, 1, amax=am[self.A_DY3]), _operand(h2, 128, 128, 1, ones_col=128),
+                              128, 129, cap, n_items, pc[0], SPLITS_ITEMS))
+        G.append(_splitk_gemm(_operand(dy2, 128, 128, 1, amax=am[self.A_DY2]), _operand(h1, 128, 128, 1, ones_col=128),
+                              128, 129, cap, n_items, pc[1], SPLITS_ITEMS))
+        G.append(_splitk_gemm(_operand(dy1, 128, 128, 1, amax=am[self.A_DY1]),
+                              _operand(fsa, 256, 281, 1, p2=vpa, ld2=32, csplit=256), 128, 281, cap, n_items, pc[2],
+                              SPLITS_ITEMS))
+        for gs in G:
+            gs.products = products
+        self.g_bwd = G
+        self.gemms = self.g_fwd + self.g_bwd
+        self.segments = [A.segment(pc[0], SPLITS_ITEMS, 128, 129, "color_branch.4", 128, 128),
+                         A.segment(pc[1], SPLITS_ITEMS, 128, 129, "color_branch.2", 128, 128),
+                         A.segment(pc[2], SPLITS_ITEMS, 128, 281, "color_branch.0", 280, 280),
+                         A.segment(_addr(self.part_c6), self.part_c6.numel() // (3 * 129), 3, 129, "color_branch.6",
+                                   128, 128)]
+        self.w6, self.b6 = W("color_branch.6")[0], A.B("color_branch.6")
+
+    def forward_and_loss(self, campos, rot, gt, lp, st):
+        """Colour forward into feat[.].yzw, then the losses, on stream st: the loss vector (sgn_loss_train's
+        8 floats), full [R, 3] and mask [R] (int8) land in self.losses / full / mask, d feat in self.dfeat."""
+        L = _lib.lib()
+        ck, p = _lib.check, _lib.ptr
+        P = self.points
+        for gs in self.g_fwd:
+            ck(L.sgn_x3_gemm(ctypes.byref(gs), st), "sgn_x3_gemm")
+        ck(L.sgn_train_colour_head(ctypes.byref(self.qo), self.n_items, p(self.h[2]), self.w6, self.b6, p(self.feat),
+                                   st), "sgn_train_colour_head")
+        ck(L.sgn_loss_train(ctypes.byref(lp), p(campos), p(rot), self.R, ctypes.byref(self.qo), p(self.feat), p(gt),
+                            p(P.points_conf), p(self.full), p(self.mask), p(self.losses), p(self.dfeat),
+                            p(P.points_conf.grad), p(self.loss_ws), self.loss_ws.numel(), st), "sgn_loss_train")
+
+    def backward(self, st):
+        """d feat -> d f_s (self.dfs) and the colour layers' weight-gradient partials, on stream st."""
+        L = _lib.lib()
+        ck, p = _lib.check, _lib.ptr
+        if self.zero_dfs:
+            self.dfs.zero_()
+        ck(L.sgn_train_colour_head_bwd(ctypes.byref(self.qo), self.n_items, p(self.h[2]), self.w6, self.b6,
+                                       p(self.dfeat), p(self.dy[2]), ctypes.c_void_p(_addr(self.amax, self.A_DY3)),
+                                       p(self.part_c6), st), "sgn_train_colour_head_bwd")
+        for gs in self.g_bwd:
+            ck(L.sgn_x3_gemm(ctypes.byref(gs), st), "sgn_x3_gemm")
+
+
 class F32Step:
     """Device buffers and pre-built launch arguments of the fp32 step for one batch capacity
     (R rays x SR samples x K neighbours), bound to one trainer's parameters and one query
     workspace.  `run` issues the step's launches on the current stream."""
 
-    # amax words (max |x| of a delta tensor, written by its producer, read by its consumers)
-    A_DY3, A_DY2, A_DY1, A_D4, A_D3, A_D2, A_D1, A_DB = range(8)
+    # amax words after the colour stage's three
+    A_D4, A_D3, A_D2, A_D1, A_DB = range(3, 8)
 
     def __init__(self, trainer, q, R):
         L = _lib.lib()
@@ -124,85 +276,28 @@ class F32Step:
         self.ext = torch.empty(rows, 8, **f32)
         self.rw = torch.empty(rows, 2, **f32)
         self.vpe = torch.empty(cap, 32, **f32)
-        self.h = [torch.empty(cap, 128, **f32) for _ in range(3)]       # colour h1, h2, h3
-        self.dy = [torch.empty(cap, 128, **f32) for _ in range(3)]      # colour dy1, dy2, dy3
-        self.dfs = torch.empty(cap, 256, **f32)
         self.d = [torch.empty(rows, 256, **f32) for _ in range(3)]      # delta1, delta2, delta3
         self.dext = torch.empty(rows, 8, **f32)
         self.dx0 = torch.empty(rows, 224, **f32)
         self.amax = torch.zeros(16, dtype=torch.int32, device=dev)
         self.dfeat = torch.empty(cap, 4, **f32)
-        self.losses = torch.zeros(8, **f32)
-        self.full = torch.empty(max(R, 1), 3, **f32)
-        self.mask = torch.empty(max(R, 1), dtype=torch.int8, device=dev)
-        self.loss_ws = torch.empty(max(int(L.sgn_loss_workspace_bytes(R, o.SR)), 16), dtype=torch.uint8, device=dev)
+        # the colour MLP and the losses over the items (their count at counts[0]), all products split-fp16
+        self.colour = ColourStage(trainer, self.qo, R, cap, _addr(self.counts, 0), self.fs, self.vpe, self.feat,
+                                  self.dfeat, self.amax)
         self.part_rows = [torch.empty(SPLITS_ROWS, 256, n, **f32)
                           for n in (257, 264, 257, 285) + ((257 + self.D,) if self.sg else ())]
-        self.part_col = [torch.empty(SPLITS_ITEMS, 128, n, **f32) for n in (129, 129, 281)]
-        self.part_c6 = torch.empty(int(L.sgn_train_head_partial_floats(0)), **f32)
         self.part_a = torch.empty(int(L.sgn_train_head_partial_floats(1)), **f32)
         self._build()
 
     # -- the launch arguments (pointers of persistent buffers: built once) ----------------------
     def _build(self):
-        tr = self.trainer
-        m, flat, shift = tr.mlp, tr.mlp.flat, tr.packer32.shift
-        g = flat.grad
-        layer_ix = {name: i for i, (name, *_) in enumerate(m.layers)}
-
-        def W(name):
-            off, o, i = m.slices[name]
-            return _addr(flat, off), o, i
-
-        def Bv(name):
-            off, o, i = m.slices[name]
-            return _addr(flat, off + o * i)
-
-        def S(name):
-            return _addr(shift, layer_ix[name])
-
+        A = _FlatAddr(self.trainer)
+        W, Bv, S = A.W, A.B, A.S
         amax = [_addr(self.amax, i) for i in range(16)]
-        n_items, n_rows = _addr(self.counts, 0), _addr(self.counts, 1)
-        cap, rc = self.cap, self.rows_cap
-        h1, h2, h3 = (_addr(t) for t in self.h)
-        dy1, dy2, dy3 = (_addr(t) for t in self.dy)
+        n_rows = _addr(self.counts, 1)
+        rc = self.rows_cap
         z1, z2, z3, z4 = (_addr(t) for t in self.z)
         d1, d2, d3 = (_addr(t) for t in self.d)
-        fs, vpe = _addr(self.fs), _addr(self.vpe)
-        G = []
-        # ---- colour forward: h = LReLU(x W^T + b) ----------------------------------------------
-        w, o_, i_ = W("color_branch.0")
-        G.append(("cf0", _rows_gemm(_operand(fs, 256, 280, 0, p2=vpe, ld2=32, csplit=256),
-                                    _operand(w, i_, i_, 0, shift=S("color_branch.0")), cap, o_, i_, n_items, h1, 128,
-                                    bias=Bv("color_branch.0"), act=1)))
-        for name, x, y in (("color_branch.2", h1, h2), ("color_branch.4", h2, h3)):
-            w, o_, i_ = W(name)
-            G.append(("cf", _rows_gemm(_operand(x, 128, 128, 0), _operand(w, i_, i_, 0, shift=S(name)), cap, o_, i_,
-                                       n_items, y, 128, bias=Bv(name), act=1)))
-        self.g_colour_fwd = G
-        # ---- colour backward: dy_prev = (dy W) * LReLU'(h_prev); d f_s = dy1 W0[:, :256] ----------
-        G = []
-        for name, dyi, mk, dyo, ai, ao in (("color_branch.4", dy3, h2, dy2, self.A_DY3, self.A_DY2),
-                                           ("color_branch.2", dy2, h1, dy1, self.A_DY2, self.A_DY1)):
-            w, o_, i_ = W(name)
-            G.append((name, _rows_gemm(_operand(dyi, 128, 128, 0, amax=amax[ai]), _operand(w, i_, i_, 1, shift=S(name)),
-                                       cap, i_, o_, n_items, dyo, 128, mask=mk, ldm=128, amax_out=amax[ao])))
-        w, o_, i_ = W("color_branch.0")
-        G.append(("dfs", _rows_gemm(_operand(dy1, 128, 128, 0, amax=amax[self.A_DY1]),
-                                    _operand(w, i_, 256, 1, shift=S("color_branch.0")), cap, 256, o_, n_items,
-                                    _addr(self.dfs), 256)))
-        # colour weight gradients (split-K over the items)
-        pc = self.part_col
-        G.append(("dWc4", _splitk_gemm(_operand(dy3, 128, 128, 1, amax=amax[self.A_DY3]),
-                                       _operand(h2, 128, 128, 1, ones_col=128), 128, 129, cap, n_items, _addr(pc[0]),
-                                       SPLITS_ITEMS)))
-        G.append(("dWc2", _splitk_gemm(_operand(dy2, 128, 128, 1, amax=amax[self.A_DY2]),
-                                       _operand(h1, 128, 128, 1, ones_col=128), 128, 129, cap, n_items, _addr(pc[1]),
-                                       SPLITS_ITEMS)))
-        G.append(("dWc0", _splitk_gemm(_operand(dy1, 128, 128, 1, amax=amax[self.A_DY1]),
-                                       _operand(fs, 256, 281, 1, p2=vpe, ld2=32, csplit=256), 128, 281, cap, n_items,
-                                       _addr(pc[2]), SPLITS_ITEMS)))
-        self.g_colour_bwd = G
         # ---- block3.2 forward again: z4 = LReLU(z3) W3^T + b3 -----------------------------------
         w, o_, i_ = W("block3.2")
         self.g_z4 = _rows_gemm(_operand(z3, 256, 256, 0, act=1), _operand(w, i_, i_, 0, shift=S("block3.2")), rc, o_, i_,
@@ -251,34 +346,21 @@ class F32Step:
                   else _operand(z2, 256, 256, 1, ones_col=256, act=1))
             self.g_row_dw.append(_splitk_gemm(_operand(_addr(self.db), 256, 256, 1, amax=amax[self.A_DB]), xb, 256, 257 + D,
                                               rc, n_rows, _addr(pr[4]), SPLITS_ROWS))
-        # ---- partials -> flat gradient ----------------------------------------------------------
-        segs = []
-
-        def seg(part, splits, M, N, name, n_in, bias_col):
-            off, o_, i_ = m.slices[name]
-            s = _lib.PartialSegment()
-            s.part, s.splits, s.M, s.N, s.n_in, s.bias_col, s.ldw = part, splits, M, N, n_in, bias_col, i_
-            s.dst_w, s.dst_b = _addr(g, off), _addr(g, off + o_ * i_)
-            segs.append(s)
-        seg(_addr(pc[0]), SPLITS_ITEMS, 128, 129, "color_branch.4", 128, 128)
-        seg(_addr(pc[1]), SPLITS_ITEMS, 128, 129, "color_branch.2", 128, 128)
-        seg(_addr(pc[2]), SPLITS_ITEMS, 128, 281, "color_branch.0", 280, 280)
-        hb = self.part_c6.numel() // (3 * 129)
-        seg(_addr(self.part_c6), hb, 3, 129, "color_branch.6", 128, 128)
-        seg(_addr(self.part_a), self.part_a.numel() // 257, 1, 257, "alpha_branch.0", 256, 256)
-        seg(_addr(pr[0]), SPLITS_ROWS, 256, 257, "block3.2", 256, 256)
-        seg(_addr(pr[1]), SPLITS_ROWS, 256, 264, "block3.0", 263, 263)
-        seg(_addr(pr[2]), SPLITS_ROWS, 256, 257, "block1.2", 256, 256)
-        seg(_addr(pr[3]), SPLITS_ROWS, 256, 285, "block1.0", 284, 284)
+        # ---- partials -> flat gradient: the colour stage's segments, then the rows' ----------------
+        segs = self.colour.segments + [
+            A.segment(_addr(self.part_a), self.part_a.numel() // 257, 1, 257, "alpha_branch.0", 256, 256),
+            A.segment(_addr(pr[0]), SPLITS_ROWS, 256, 257, "block3.2", 256, 256),
+            A.segment(_addr(pr[1]), SPLITS_ROWS, 256, 264, "block3.0", 263, 263),
+            A.segment(_addr(pr[2]), SPLITS_ROWS, 256, 257, "block1.2", 256, 256),
+            A.segment(_addr(pr[3]), SPLITS_ROWS, 256, 285, "block1.0", 284, 284)]
         if self.sg:
-            seg(_addr(pr[4]), SPLITS_ROWS, 256, 257 + self.D, "block2_bpnet.0", 256 + self.D, 256 + self.D)
+            segs.append(A.segment(_addr(pr[4]), SPLITS_ROWS, 256, 257 + self.D, "block2_bpnet.0", 256 + self.D,
+                                  256 + self.D))
         self.segs = (_lib.PartialSegment * len(segs))(*segs)
         self.n_seg = len(segs)
-        self.w6, self.b6 = W("color_branch.6")[0], Bv("color_branch.6")
         self.wa, self.ba = W("alpha_branch.0")[0], Bv("alpha_branch.0")
-        self.grad_key = (flat.data_ptr(), g.data_ptr())
-        self.bpack = _attach_bpack([gs for _, gs in self.g_colour_fwd + self.g_colour_bwd + self.g_row_bwd] +
-                                   [self.g_z4] + self.g_row_dw, flat.device)
+        self.bpack = _attach_bpack(self.colour.gemms + [gs for _, gs in self.g_row_bwd] + [self.g_z4] + self.g_row_dw,
+                                   A.flat.device)
 
     # -- one step ------------------------------------------------------------------------------
     def run(self, pt, proj, blob, campos, rot, gt, lp):
@@ -287,7 +369,7 @@ class F32Step:
         vector (sgn_loss_train's 8 floats), the rendered colour [R, 3] and the ray mask [R] (int8)."""
         L = _lib.lib()
         st = _lib.stream_handle()
-        tr, K, qo = self.trainer, self.K, self.qo
+        tr, K, qo, col = self.trainer, self.K, self.qo, self.colour
         P = tr.points
         ck = _lib.check
         cap, p = self.cap, _lib.ptr
@@ -312,21 +394,11 @@ class F32Step:
         if self.D:
             ck(L.sgn_train_row_gather(ctypes.byref(qo), K, p(self.row_off), p(self.counts), p(tr.bpnet32), self.D,
                                       p(self.bprow), st), "sgn_train_row_gather")
-        for _, gs in self.g_colour_fwd:
-            gemm(gs)
-        ck(L.sgn_train_colour_head(ctypes.byref(qo), p(self.counts), p(self.h[2]), self.w6, self.b6, p(self.feat), st),
-           "sgn_train_colour_head")
-        ck(L.sgn_loss_train(ctypes.byref(lp), p(campos), p(rot), self.R, ctypes.byref(qo), p(self.feat), p(gt),
-                            p(P.points_conf), p(self.full), p(self.mask), p(self.losses), p(self.dfeat),
-                            p(P.points_conf.grad), p(self.loss_ws), self.loss_ws.numel(), st), "sgn_loss_train")
-        ck(L.sgn_train_colour_head_bwd(ctypes.byref(qo), p(self.counts), p(self.h[2]), self.w6, self.b6, p(self.dfeat),
-                                       p(self.dy[2]), ctypes.c_void_p(_addr(self.amax, self.A_DY3)), p(self.part_c6), st),
-           "sgn_train_colour_head_bwd")
-        for _, gs in self.g_colour_bwd:
-            gemm(gs)
+        col.forward_and_loss(campos, rot, gt, lp, st)
+        col.backward(st)
         gemm(self.g_z4)
         ck(L.sgn_train_row_head(ctypes.byref(pt), ctypes.byref(qo), K, p(self.row_off), p(self.counts), p(self.z[3]),
-                                p(self.dfs), p(self.dfeat), p(self.rw), self.wa, self.ba, p(P.points_conf.grad),
+                                p(col.dfs), p(self.dfeat), p(self.rw), self.wa, self.ba, p(P.points_conf.grad),
                                 ctypes.c_void_p(_addr(self.amax, self.A_D4)), p(self.part_a), st), "sgn_train_row_head")
         for _, gs in self.g_row_bwd:
             gemm(gs)
@@ -337,143 +409,101 @@ class F32Step:
         for gs in self.g_row_dw:
             gemm(gs)
         ck(L.sgn_reduce_partials(self.n_seg, self.segs, st), "sgn_reduce_partials")
-        return self.losses, self.full[:self.R], self.mask[:self.R]
+        return col.losses, col.full[:self.R], col.mask[:self.R]
 
 
-class ColourStep:
-    """The colour MLP, the losses and their backward for the f16 training step on the same hand-written
-    kernels as F32Step (precision "f16" only changes the row MLP): items are the query's work-list
-    positions (k_agg_rows' f_s rows), `cap` of them at most, the device count at q.counters[1].
-    Per step (PE(viewdir) arrives from sgn_colour_inputs): 3 x sgn_x3_gemm forward + sgn_train_colour_head
-    (rgb into feat), sgn_loss_train,
-    the colour backward (head, 2 masked dy W, d f_s = dy1 W0[:, :256]; one fp16 product per multiply-add,
-    the step's delta precision), the three weight gradients as
-    split-K partials and one sgn_reduce_partials into the flat gradient.  No autograd, no host sync: it
-    runs inside the f16 step's captured graph."""
+class F32Runner:
+    """What `train_hip.HipTrainer` runs at precision "f32" between its shared prologue (inputs, query)
+    and epilogue (all-reduce, point-row exchange): the reference's fp32 step as HIP launches with the
+    counts on the device -- no host sync on one GPU; under DP one for the touched-row counts.
 
-    A_DY3, A_DY2, A_DY1 = range(3)
+      begin   the fp32-faithful blob re-packed, the point Adam's launch (HipTrainer._adam_rows: on the
+              query's table, whose distinct-row list is then the step's touched list; under DP on the
+              rank's touched rows, which ride the point-row exchange)
+      run     sgn_point_project_f32_subset (block1.0's per-point part for the touched points only: ~50 k
+              of 1.2 M for a 4096-ray batch -- the rows read no other point, and the weights change
+              every step), F32Step.run, the results out into one fresh allocation"""
 
-    def __init__(self, trainer, q, cap, fs32, vdir, feat, R, products=1):
-        """products: of the backward GEMMs, 1 (the f16 step's delta precision: one fp16 product per
-        multiply-add) or 3 (split-fp16 at fp32 accuracy); the forward keeps 3, so the rendered colour and
-        the losses are the eager fp32 colour MLP's."""
+    graph_captures = 0   # no captured graphs at this precision
+
+    def __init__(self, trainer):
+        self.tr = trainer
+        self.step = None         # the F32Step of the last batch's capacity and buffers (`key`)
+        self.key = None
+        self.proj = None         # block1.0's per-point projection, grown on demand
+        self._blob = None        # this step's fp32-faithful blob (begin)
+        self._rows = None        # this step's touched points: (int32 list, device count)
+        self._t_idx = self._t_cnt = None   # under DP: touched_rows' list and count
+        # without the row-sparse Adam the touched list comes from sgn_touched_points' stamp table
+        self._stamp = self._tlist = self._tcount = None
+        self._stamp_n, self._tstep = -1, 0
+
+    def _touched(self, q, npts):
+        """The step's touched points (sgn_touched_points: an int32 list in no particular order and
+        its device count), for the single-GPU projection subset; no host sync, one launch."""
+        tr, dev = self.tr, self.tr.device
+        if self._stamp_n != npts:
+            self._stamp = torch.full((npts,), -1, dtype=torch.int32, device=dev)
+            self._tlist = torch.empty(npts, dtype=torch.int32, device=dev)
+            self._tcount = torch.zeros(3, dtype=torch.int64, device=dev)   # [2]: out-of-range ids met
+            self._stamp_n, self._tstep = npts, 0
+        step = self._tstep
+        self._tstep = (step + 1) & 0x7fffffff
+        if self._tstep == 0:   # the stamp table outlived 2^31 steps: start it again
+            self._stamp_n = -1
+        K = tr.opts.K
+        tr._check_oob()
+        _lib.check(_lib.lib().sgn_touched_points(_lib.ptr(q.pidx), _lib.ptr(q.counters), q.pidx.numel() // K, K, npts,
+                                                 step, _lib.ptr(self._stamp), _lib.ptr(self._tlist),
+                                                 _lib.ptr(self._tcount), _lib.stream_handle()), "sgn_touched_points")
+        tr._watch_oob(self._tcount[2:3])
+        return self._tlist, self._tcount[step & 1]
+
+    def begin(self, b):
+        """What the step queues before the gradients are made ready: the blob and the point Adam's launch."""
+        tr, q = self.tr, b.q
+        K, npts = tr.opts.K, tr.points.xyz.shape[0]
+        self._blob = tr.packer32.pack(tr.mlp.flat)
+        if b.dp:   # every rank's touched rows ride the step's one sync (the point-row exchange)
+            self._t_idx, self._t_cnt = touched_rows(q.pidx, q.counters[0], K, npts)
+            self._rows = (self._t_idx.to(torch.int32), self._t_cnt)
+            tr._adam_rows(*self._rows, True, 1)
+        else:      # the Adam's distinct-row list is the step's touched list (row 0 included)
+            self._rows = tr._adam_rows(q.pidx, q.counters, False, K) or self._touched(q, npts)
+
+    def run(self, b):
+        """Forward + backward of the batch into the (ready) gradients.  Returns (loss parts, rendered
+        colour [R, 3], ray_mask [R] int8)."""
+        tr, dev = self.tr, self.tr.device
+        q, R = b.q, b.R
         L = _lib.lib()
-        self.trainer, self.q, self.cap, self.R = trainer, q, max(cap, 1), R
-        self.products = products
-        self.qo = q.abi()
-        dev = trainer.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        cap = self.cap
-        self.fs32, self.vdir, self.feat = fs32, vdir, feat
-        self.vpe = torch.zeros(cap, 32, **f32)     # sgn_colour_inputs: PE(viewdir), the ones column 24, zeros
-        self.h = [torch.empty(cap, 128, **f32) for _ in range(3)]
-        self.dy = [torch.empty(cap, 128, **f32) for _ in range(3)]
-        self.dfs = torch.empty(cap, 256, **f32)
-        self.amax = torch.zeros(4, dtype=torch.int32, device=dev)
-        self.dfeat = torch.zeros(feat.shape[0] + 1, 4, **f32)   # + the padding items' zero row
-        self.losses = torch.zeros(8, **f32)
-        self.full = torch.empty(max(R, 1), 3, **f32)
-        self.mask = torch.empty(max(R, 1), dtype=torch.int8, device=dev)
-        self.loss_ws = torch.empty(max(int(L.sgn_loss_workspace_bytes(R, trainer.opts.SR)), 16), dtype=torch.uint8,
-                                   device=dev)
-        self.part_col = [torch.empty(SPLITS_ITEMS, 128, n, **f32) for n in (129, 129, 281)]
-        self.part_c6 = torch.empty(int(L.sgn_train_head_partial_floats(0)), **f32)
-        self._build()
+        pt = tr._tables(b.campos, b.rot, b.raydir)
+        nproj = int(L.sgn_point_proj_bytes_f32(tr.points.xyz.shape[0]))
+        if self.proj is None or self.proj.numel() < nproj:
+            self.proj = torch.empty(max(nproj, 16), dtype=torch.uint8, device=dev)
+        idx32, cnt = self._rows
+        _lib.check(L.sgn_point_project_f32_subset(ctypes.byref(pt), _lib.ptr(self._blob), _lib.ptr(idx32),
+                                                  _lib.ptr(cnt), _lib.ptr(self.proj), _lib.stream_handle()),
+                   "sgn_point_project_f32_subset")
+        fl = tr.mlp.flat
+        key = (R, q.work.data_ptr(), q.pidx.data_ptr(), fl.data_ptr(), fl.grad.data_ptr())
+        if self.key != key:
+            self.step, self.key = F32Step(tr, q, R), key
+        losses, full, mask = self.step.run(pt, self.proj, self._blob, b.campos, b.rot, b.gt, tr._loss_params(b.bg_ray))
+        # the step's buffers are reused by the next step: the losses, the colour and the mask out into
+        # one fresh allocation (one launch), as the f16 step's graph outputs
+        nl = losses.numel()
+        buf = torch.empty(nl + 3 * R + -(-R // 4), dtype=torch.float32, device=dev)
+        lo, full_o = buf[:nl], buf[nl:nl + 3 * R].view(R, 3)
+        mask_o = buf[nl + 3 * R:].view(torch.int8)[:R]
+        _lib.copy_segments([(losses, lo), (full, full_o), (mask, mask_o)])
+        parts = {"ray_masked_coarse_raycolor": lo[0], "ray_miss_coarse_raycolor": lo[2],
+                 "coarse_raycolor": lo[3], "conf_coefficient": lo[1], "total": lo[0] + 3e-6 + 1e-4 * lo[1]}
+        return parts, full_o, mask_o
 
-    def _build(self):
-        tr = self.trainer
-        m, flat, shift = tr.mlp, tr.mlp.flat, tr.packer32.shift
-        g = flat.grad
-        layer_ix = {name: i for i, (name, *_) in enumerate(m.layers)}
+    def dp_rows(self):
+        """Under DP: this rank's touched rows and every rank's count (gathered and read here: the
+        step's one host sync, after the flat gradient's all-reduce is queued)."""
+        return self._t_idx, [int(x) for x in gather_counts(self._t_cnt).tolist()]
 
-        def W(name):
-            off, o, i = m.slices[name]
-            return _addr(flat, off), o, i
 
-        def Bv(name):
-            off, o, i = m.slices[name]
-            return _addr(flat, off + o * i)
-
-        def S(name):
-            return _addr(shift, layer_ix[name])
-
-        amax = [_addr(self.amax, i) for i in range(4)]
-        n_items = _addr(self.q.counters, 1)         # the work-list length
-        cap = self.cap
-        h1, h2, h3 = (_addr(t) for t in self.h)
-        dy1, dy2, dy3 = (_addr(t) for t in self.dy)
-        fs, vpe = _addr(self.fs32), _addr(self.vpe)
-        w, o_, i_ = W("color_branch.0")
-        G = [_rows_gemm(_operand(fs, 256, 280, 0, p2=vpe, ld2=32, csplit=256), _operand(w, i_, i_, 0, shift=S("color_branch.0")),
-                        cap, o_, i_, n_items, h1, 128, bias=Bv("color_branch.0"), act=1)]
-        for name, x, y in (("color_branch.2", h1, h2), ("color_branch.4", h2, h3)):
-            w, o_, i_ = W(name)
-            G.append(_rows_gemm(_operand(x, 128, 128, 0), _operand(w, i_, i_, 0, shift=S(name)), cap, o_, i_, n_items,
-                                y, 128, bias=Bv(name), act=1))
-        self.g_fwd = G
-        G = []
-        for name, dyi, mk, dyo, ai, ao in (("color_branch.4", dy3, h2, dy2, self.A_DY3, self.A_DY2),
-                                           ("color_branch.2", dy2, h1, dy1, self.A_DY2, self.A_DY1)):
-            w, o_, i_ = W(name)
-            G.append(_rows_gemm(_operand(dyi, 128, 128, 0, amax=amax[ai]), _operand(w, i_, i_, 1, shift=S(name)), cap, i_, o_,
-                                n_items, dyo, 128, mask=mk, ldm=128, amax_out=amax[ao]))
-        w, o_, i_ = W("color_branch.0")
-        G.append(_rows_gemm(_operand(dy1, 128, 128, 0, amax=amax[self.A_DY1]), _operand(w, i_, 256, 1, shift=S("color_branch.0")),
-                            cap, 256, o_, n_items, _addr(self.dfs), 256))
-        pc = self.part_col
-        G.append(_splitk_gemm(_operand(dy3, 128, 128, 1, amax=amax[self.A_DY3]), _operand(h2, 128, 128, 1, ones_col=128),
-                              128, 129, cap, n_items, _addr(pc[0]), SPLITS_ITEMS))
-        G.append(_splitk_gemm(_operand(dy2, 128, 128, 1, amax=amax[self.A_DY2]), _operand(h1, 128, 128, 1, ones_col=128),
-                              128, 129, cap, n_items, _addr(pc[1]), SPLITS_ITEMS))
-        G.append(_splitk_gemm(_operand(dy1, 128, 128, 1, amax=amax[self.A_DY1]),
-                              _operand(fs, 256, 281, 1, p2=vpe, ld2=32, csplit=256), 128, 281, cap, n_items, _addr(pc[2]),
-                              SPLITS_ITEMS))
-        self.g_bwd = G
-        for gs in self.g_bwd:
-            gs.products = self.products
-        segs = []
-
-        def seg(part, splits, M, N, name, n_in, bias_col):
-            off, o_, i_ = m.slices[name]
-            s = _lib.PartialSegment()
-            s.part, s.splits, s.M, s.N, s.n_in, s.bias_col, s.ldw = part, splits, M, N, n_in, bias_col, i_
-            s.dst_w, s.dst_b = _addr(g, off), _addr(g, off + o_ * i_)
-            segs.append(s)
-        seg(_addr(pc[0]), SPLITS_ITEMS, 128, 129, "color_branch.4", 128, 128)
-        seg(_addr(pc[1]), SPLITS_ITEMS, 128, 129, "color_branch.2", 128, 128)
-        seg(_addr(pc[2]), SPLITS_ITEMS, 128, 281, "color_branch.0", 280, 280)
-        seg(_addr(self.part_c6), self.part_c6.numel() // (3 * 129), 3, 129, "color_branch.6", 128, 128)
-        self.segs = (_lib.PartialSegment * len(segs))(*segs)
-        self.n_seg = len(segs)
-        self.w6, self.b6 = W("color_branch.6")[0], Bv("color_branch.6")
-        self.bpack = _attach_bpack(self.g_fwd + self.g_bwd, flat.device)
-
-    def run(self, campos, rot, gt, lp):
-        """Colour forward into feat[.].yzw, the losses, the colour backward: returns the loss vector
-        (sgn_loss_train's 8 floats), full [R, 3], mask [R] (int8), d f_s [cap, 256] and d feat [S, 4]
-        (alpha's gradient in .x); the colour weight gradients are added into flat.grad, the zero-one
-        gradients into points_conf.grad."""
-        L = _lib.lib()
-        st = _lib.stream_handle()
-        ck, p = _lib.check, _lib.ptr
-        tr, qo = self.trainer, self.qo
-        P = tr.points
-        cnt = ctypes.c_void_p(_addr(self.q.counters, 1))
-        # self.vpe (PE(viewdir) | 1 | 0) was written by sgn_colour_inputs with the items' other inputs
-        self.amax.zero_()
-        for gs in self.g_fwd:
-            ck(L.sgn_x3_gemm(ctypes.byref(gs), st), "sgn_x3_gemm")
-        ck(L.sgn_train_colour_head(ctypes.byref(qo), cnt, p(self.h[2]), self.w6, self.b6, p(self.feat), st),
-           "sgn_train_colour_head")
-        ck(L.sgn_loss_train(ctypes.byref(lp), p(campos), p(rot), self.R, ctypes.byref(qo), p(self.feat), p(gt),
-                            p(P.points_conf), p(self.full), p(self.mask), p(self.losses), p(self.dfeat),
-                            p(P.points_conf.grad), p(self.loss_ws), self.loss_ws.numel(), st), "sgn_loss_train")
-        # d f_s of the padding items stays 0: the f16 backward's loss scale is the max over all cap rows
-        self.dfs.zero_()
-        ck(L.sgn_train_colour_head_bwd(ctypes.byref(qo), cnt, p(self.h[2]), self.w6, self.b6, p(self.dfeat), p(self.dy[2]),
-                                       ctypes.c_void_p(_addr(self.amax, self.A_DY3)), p(self.part_c6), st),
-           "sgn_train_colour_head_bwd")
-        for gs in self.g_bwd:
-            ck(L.sgn_x3_gemm(ctypes.byref(gs), st), "sgn_x3_gemm")
-        ck(L.sgn_reduce_partials(self.n_seg, self.segs, st), "sgn_reduce_partials")
-        return self.losses, self.full[:self.R], self.mask[:self.R], self.dfs, self.dfeat

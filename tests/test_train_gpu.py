@@ -590,6 +590,50 @@ def test_data_parallel_step_matches_single_rank(precision, monkeypatch):
         assert err[k] <= max(UPDATE_TOL if precision == "f16" else 1e-2, 3 * spread[k]), (k, err, spread)
 
 
+@pytest.mark.parametrize("precision", ["f32", "f16"])
+def test_optimizers_stepped_by_hand_match_apply(precision):
+    """backward(A); apply(); backward(B); apply() against the same with the first apply() spelled out
+    (_set_lr, both optimizers' step(), step_count): without apply() the gradients are not known to be
+    clean, so backward(B) zeroes them -- which must happen after the row-sparse Adam's launch has
+    applied step A's deferred point update, or that update runs with g = 0 and the touched rows do
+    not move.  The parameters differ only by the atomic accumulation order of the point gradients,
+    bounded as test_data_parallel_step_matches_single_rank bounds it: by the spread of the apply()
+    sequence run twice."""
+    pc, view, qd, mlp, gt = _setup(seed=7)
+    d = lambda a: torch.from_numpy(a).to(DEV)  # noqa: E731
+    names = ("points_embeding", "points_color", "points_dir", "points_conf")
+    runs = {}
+    for mode in ("apply", "apply_again", "by_hand"):
+        points = PointParams(pc.xyz, pc.embedding, pc.color, pc.dir, pc.conf, DEV)
+        tr = HipTrainer(points, mlp, dataclasses_replace(O), DEV, precision=precision)
+        p0 = {k: getattr(points, k).detach().clone() for k in names}
+        p0["mlp"] = tr.mlp.flat.detach().clone()
+        for it in range(2):
+            torch.manual_seed(100 + it)
+            gti = torch.rand(gt.shape, generator=torch.Generator().manual_seed(it)).to(DEV)
+            tr.backward(d(view.campos), d(view.camrotc2w), d(view.raydir), 0.1, 8.0, gti)
+            if mode == "by_hand" and it == 0:
+                tr._set_lr()
+                tr.opt_net.step()
+                tr.opt_pts.step()
+                tr.step_count += 1
+            else:
+                tr.apply()
+        tr.sync_points()
+        upd = {k: getattr(points, k).detach() - p0[k] for k in names}
+        upd["mlp"] = tr.mlp.flat.detach() - p0["mlp"]
+        runs[mode] = upd
+    rel = lambda x, y: {k: float(torch.linalg.vector_norm((x[k] - y[k]).double())  # noqa: E731
+                                 / torch.linalg.vector_norm(y[k].double())) for k in y}
+    spread = rel(runs["apply_again"], runs["apply"])
+    err = rel(runs["by_hand"], runs["apply"])
+    print("apply() spread", {k: f"{v:.1e}" for k, v in spread.items()})
+    print("by hand vs apply()", {k: f"{v:.1e}" for k, v in err.items()})
+    for k in err:
+        assert float(torch.linalg.vector_norm(runs["by_hand"][k])) > 0
+        assert err[k] <= max(UPDATE_TOL if precision == "f16" else 1e-2, 3 * spread[k]), (k, err, spread)
+
+
 @pytest.mark.parametrize("rows", [0, 1, 777, 165_000])
 def test_colsum_matches_torch_sum(rows):
     """sgn_colsum_f16 (bias gradients) against a float64 column sum of the same fp16 tiles,
@@ -676,7 +720,7 @@ def test_graph_captured_step_matches_eager_step():
         params["mlp"] = tr.mlp.flat.detach().cpu().clone() - p0["mlp"]
         runs[use_graph] = (losses, grads, params, first)
         if use_graph is True:
-            assert tr._graphs, "the graph path did not run"
+            assert tr.stepper._graphs, "the graph path did not run"
     (le, ge, pe, fe), (lg, gg, pg, fg) = runs[False], runs[True]
     # run-to-run spread of the eager path itself (atomic accumulation order in the backward)
     pe2 = runs["eager2"][2]
@@ -696,7 +740,7 @@ def test_graph_captured_step_matches_eager_step():
     assert abs(le[0] - lg[0]) <= 1e-5 * abs(le[0])
     for a, b in zip(le, lg):
         assert abs(a - b) <= 1e-3 * abs(a)
-    # the graph path's colour backward multiplies in fp16 (ColourStep products=1, the step's delta
+    # the graph path's colour backward multiplies in fp16 (ColourStage products=1, the step's delta
     # precision) where the eager path's torch autograd runs fp32: measured 7.2e-4 (block3.2), every
     # tensor far inside the f16 step's bars against fp32 autograd (GRAD_TOL_MLP / GRAD_TOL_POINTS)
     assert max(ge_err.values()) <= 2e-3, ge_err
@@ -726,7 +770,7 @@ def test_graph_step_without_hits():
             assert float(g.abs().max()) == 0.0, k
         tr.apply()
         assert all(torch.isfinite(getattr(points, k)).all() for k in ("points_embeding", "points_conf"))
-    assert tr._graphs, "the graph path did not run"
+    assert tr.stepper._graphs, "the graph path did not run"
 
 
 def test_f32_step_without_hits():
@@ -890,7 +934,7 @@ def test_graph_cache_buckets_and_lru(monkeypatch):
     """Loss-stage graphs per capacity bucket: a batch of another size captures a second graph,
     returning to the first size replays the first (LRU hit, no capture); with room for one
     graph every change recaptures.  Each replayed step equals the eager step's loss."""
-    import sgnerf_amd.train_hip as th
+    import sgnerf_amd.train_f16 as th
     pc, view, qd, mlp, gt = _setup(seed=7)
     d = lambda a: torch.from_numpy(a).to(DEV)  # noqa: E731
     sizes = [view.raydir.shape[0], view.raydir.shape[0] // 3, view.raydir.shape[0]]
@@ -910,11 +954,11 @@ def test_graph_cache_buckets_and_lru(monkeypatch):
         return tr, out
     _, eager = run(False, 8)
     tr, graph = run(True, 8)
-    assert tr.graph_captures == 2 and len(tr._graphs) == 2
+    assert tr.graph_captures == 2 and len(tr.stepper._graphs) == 2
     for a, b in zip(eager, graph):
         assert abs(a - b) <= 1e-5 * abs(a), (eager, graph)
     tr1, _ = run(True, 1)
-    assert tr1.graph_captures == 3 and len(tr1._graphs) == 1
+    assert tr1.graph_captures == 3 and len(tr1.stepper._graphs) == 1
 
 
 def test_200_step_training_tracks_fp32_torch():

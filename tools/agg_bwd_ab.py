@@ -67,7 +67,8 @@ torch.cuda.synchronize()
 tr, a = rec["tr"], rec["args"]
 n = int(a[4 if sg else 2])
 P = tr.points
-outs = [tr.d[0], tr.d[1], tr.d[2], tr.d[3], tr.h4, tr.dza] + ([tr.db] if sg else [])
+f16 = tr.stepper   # the F16Step's row buffers
+outs = [f16.d[0], f16.d[1], f16.d[2], f16.d[3], f16.h4, f16.dza] + ([f16.db] if sg else [])
 grads = [P.points_embeding.grad, P.points_color.grad, P.points_dir.grad, P.points_conf.grad]
 
 

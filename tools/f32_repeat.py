@@ -33,7 +33,7 @@ n_runs = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 for it in range(n_runs):
     parts, full, mask = tr.backward(campos, rot, raydir, 0.1, 8.0, gt)
     torch.cuda.synchronize()
-    st = tr._f32step
+    st = tr.stepper.step   # the F32Step of this batch capacity
     n, rows = [int(x) for x in st.counts[:2].tolist()]
     S = int(st.q.counters[0])
     ws = st.ws32
@@ -41,7 +41,7 @@ for it in range(n_runs):
     rows_t = ws[ws_items * 1024:ws_items * 1024 + ws_items * 32].view(torch.int32).view(-1, 8)
     slots_t = ws[ws_items * 1056:ws_items * 1056 + ws_items * 16].view(torch.int32).view(-1, 4)
     nslot = int(ws[ws_items * 1072:ws_items * 1072 + 4].view(torch.int32)[0])
-    snap = {"rows_tab": rows_t[:nslot].clone(), "slots_tab": slots_t[:nslot].clone(), "full": full.clone(), "feat": st.feat[:S].clone(), "fs": st.fs[:n].clone(), "h3": st.h[2][:n].clone(),
+    snap = {"rows_tab": rows_t[:nslot].clone(), "slots_tab": slots_t[:nslot].clone(), "full": full.clone(), "feat": st.feat[:S].clone(), "fs": st.fs[:n].clone(), "h3": st.colour.h[2][:n].clone(),
             "z1": st.z[0][:rows].clone(), "z3": st.z[2][:rows].clone(), "work": st.q.work[:n].clone(),
             "pidx": st.q.pidx[:S * 8].clone(), "grad": tr.mlp.flat.grad.clone(),
             "g_emb": points.points_embeding.grad.clone()}
