@@ -41,7 +41,7 @@ extern "C" {
 typedef void *sgn_stream_t; /* hipStream_t (torch.cuda.current_stream().cuda_stream) */
 typedef struct sgn_grid sgn_grid; /* opaque, device-resident voxel grid of one point cloud */
 
-#define SGN_ABI_VERSION 20
+#define SGN_ABI_VERSION 21
 
 /* ---- grid ------------------------------------------------------------- */
 
@@ -122,17 +122,26 @@ int sgn_query(const sgn_grid *grid, const sgn_query_params *qp, const float *d_c
               const sgn_query_out *out, void *d_workspace, size_t workspace_bytes,
               sgn_stream_t stream);
 
-/* ---- aggregator (per-neighbour MLP + K-blend, colour MLP) -------------- */
-
-/* Size in bytes of the packed fp16 weight blob for the ScanNet-layout viewmlp
- * (block1 284->256->256, block3 263->256->256, alpha 256->1, colour 280->128x3->3). */
-size_t sgn_mlp_packed_bytes(void);
-/* Packs fp32 nn.Linear weights (row-major [out][in]) + biases into the
- * MFMA fragment-major fp16 layout.  Host pointers in, device pointer out
- * (synchronous copy). Order of `w`/`b`: block1.0, block1.2, block3.0,
- * block3.2, alpha_branch.0, color_branch.0, .2, .4, .6 (9 layers). */
-int sgn_mlp_pack(const float *const *w, const float *const *b, void *d_packed,
-                 sgn_stream_t stream);
+/* ---- aggregator (per-neighbour MLP + K-blend, colour MLP) --------------
+ * The network is the ScanNet-layout viewmlp (block1 284->256->256, block3 263->256->256, alpha
+ * 256->1, colour 280->128x3->3), optionally with SG-NeRF's block2_bpnet
+ * (shading_feature_mlp_layer2_bpnet; PointAggregator.block2_bpnet, point_aggregators.py:345-354,
+ * applied at :629-636, and the BPNet-embedding gather of NeuralPoints.forward,
+ * neural_points.py:970-972): Linear(256 + bpnet_dim -> 256) + LReLU on [block1 output |
+ * bpnet_points_embedding[pidx]] between block1 and block3.
+ *
+ * THE VARIANT.  Every function that depends on it takes (bpnet_layers, bpnet_dim) first:
+ *   (0, 0)   the base network;
+ *   (1, 96)  block2_bpnet with the BPNet embedding (predict_semantic = 1, semantic_guidance = 1);
+ *   (1, 0)   block2_bpnet alone (predict_semantic = 0).
+ * Anything else is an argument error (sizing functions return 0).  Arguments that only block2_bpnet
+ * needs are marked "SG": they are required with bpnet_layers = 1 (the BPNet tables with bpnet_dim > 0)
+ * and may be NULL otherwise.
+ *
+ * Weight order of every `w` / `b` (host arrays of fp32 nn.Linear weights, row-major [out][in], and
+ * biases): block1.0, block1.2, block3.0, block3.2, alpha_branch.0, color_branch.0, .2, .4, .6; SG:
+ * block2_bpnet.0 ([256][256 + bpnet_dim]) as entry 9.  The flat parameter vector of the index maps
+ * holds the same layers in this order, each weight then its bias. */
 
 typedef struct {
     /* point tables, row = neural point index */
@@ -154,56 +163,43 @@ typedef struct {
     const float *samp_pers;  /* [S,3] or NULL (with pers) */
 } sgn_point_tables;
 
-/* out_feat: float4[S] = [alpha_s, r, g, b] for every work-list sample (samples
- * without a valid neighbour are not written; the composite ignores them).
- * Optional (NULL to skip): out_blend float[S*K] = normalised weight * conf
- * (the reference's `weight * conf_coefficient`), out_wnorm float[S*K] = normalised
- * weight alone (the reference's `weight` output, point_aggregators.py:946-958). */
-size_t sgn_aggregate_workspace_bytes(int64_t S);
-/* stages: bit 0 = per-neighbour MLP + K-blend (writes alpha), bit 1 = colour MLP (rgb). */
-int sgn_aggregate(const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity,
-                  int32_t K, const void *d_packed_mlp, float *d_out_feat, float *d_out_blend,
-                  float *d_out_wnorm, void *d_workspace, size_t workspace_bytes, int32_t stages,
-                  sgn_stream_t stream);
-
-/* ---- split block1.0 (per-point projection) ----------------------------------
- * block1.0's inputs [feat | PE(feat) | PE(dists)] (point_aggregators.py:594-621) are per
- * point for the first 224 of 284 channels: sgn_point_project computes
- * P[p] = W0a [feat_p | PE(feat_p)] + b0 for every point once per frame (fp16,
- * sgn_point_proj_bytes(N)), and sgn_aggregate_sg(d_point_proj = P) then multiplies only the
- * 60 PE(dists) channels per (sample, neighbour) row.  Same sums, regrouped. */
-size_t sgn_point_proj_bytes(int64_t n_points);
-int sgn_point_project(const sgn_point_tables *pt, const void *d_packed_mlp, void *d_proj,
-                      sgn_stream_t stream);
-/* sgn_point_project for the points d_idx[0 .. *d_count) only (ABI 20; int32 indices < n_points, int64
- * device count, e.g. sgn_frame_points' list): the f16 renderer projects the points a frame's
- * samples name.  The other points' P rows are left as they are. */
-int sgn_point_project_subset(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
-                             const int64_t *d_count, void *d_proj, sgn_stream_t stream);
-/* Byte offsets inside the packed blob: 0 = fp32 section, 1 = split block1.0 sections,
- * 2 = end of the base blob (sgn_mlp_packed_bytes). */
+/* The packed fp16 weight blob (MFMA fragment-major): its size, and the pack from host weights to a
+ * device blob (synchronous copy).  sgn_mlp_section: byte offsets inside it, 0 = fp32 section,
+ * 1 = split block1.0 sections, 2 = end of the base part (= sgn_mlp_packed_bytes(0, 0); the SG
+ * sections follow, so the base layout is a prefix of every variant's). */
+size_t sgn_mlp_packed_bytes(int32_t bpnet_layers, int32_t bpnet_dim);
+int sgn_mlp_pack(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
+                 void *d_packed, sgn_stream_t stream);
 size_t sgn_mlp_section(int32_t which);
-
-/* ---- SG-NeRF variant: block2_bpnet (shading_feature_mlp_layer2_bpnet) ---
- * Replaces PointAggregator.block2_bpnet (models/aggregators/point_aggregators.py:345-354,
- * applied at :629-636) and the BPNet-embedding gather of NeuralPoints.forward
- * (models/neural_points/neural_points.py:970-972): Linear(256 + bpnet_dim -> 256) + LReLU
- * on [block1 output | bpnet_points_embedding[pidx]] between block1 and block3.
- * Supported: bpnet_layers 0 (= the base functions above), or 1 with bpnet_dim 96
- * (predict_semantic = 1, semantic_guidance = 1) or 0 (predict_semantic = 0).
- * Weight order: the 9 base layers, then block2_bpnet.0 ([256][256 + bpnet_dim]). */
-size_t sgn_mlp_packed_bytes_sg(int32_t bpnet_layers, int32_t bpnet_dim); /* 0: unsupported */
-int sgn_mlp_pack_sg(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w,
-                    const float *const *b, void *d_packed, sgn_stream_t stream);
-/* bpnet_points_embedding f32[N, 96] -> fp16 [N, 96] (the table sgn_aggregate_sg gathers;
- * the reference holds it detached, neural_points.py:662). 16-byte aligned pointers. */
+/* SG: bpnet_points_embedding f32[N, 96] -> fp16 [N, 96] (the table sgn_aggregate gathers; the
+ * reference holds it detached, neural_points.py:662).  16-byte aligned pointers. */
 int sgn_bpnet_pack(const float *d_embedding, int64_t n_points, int32_t bpnet_dim, void *d_out_f16,
                    sgn_stream_t stream);
-int sgn_aggregate_sg(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f16,
-                     const void *d_point_proj, const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity,
-                     int32_t K, const void *d_packed_mlp, float *d_out_feat, float *d_out_blend,
-                     float *d_out_wnorm, void *d_workspace, size_t workspace_bytes,
-                     int32_t stages, sgn_stream_t stream);
+
+/* Split block1.0 (per-point projection).  block1.0's inputs [feat | PE(feat) | PE(dists)]
+ * (point_aggregators.py:594-621) are per point for the first 224 of 284 channels:
+ * sgn_point_project computes P[p] = W0a [feat_p | PE(feat_p)] + b0 (fp16, sgn_point_proj_bytes(N)),
+ * and sgn_aggregate(d_point_proj = P) then multiplies only the 60 PE(dists) channels per (sample,
+ * neighbour) row.  Same sums, regrouped.  d_idx == d_count == NULL: every point.  Otherwise the
+ * points d_idx[0 .. *d_count) only (int32 indices < n_points, int64 device count, e.g.
+ * sgn_frame_points' list) and the other points' rows are left as they are; exactly one of the two
+ * being NULL is an argument error. */
+size_t sgn_point_proj_bytes(int64_t n_points);
+int sgn_point_project(const sgn_point_tables *pt, const void *d_packed_mlp, const int32_t *d_idx,
+                      const int64_t *d_count, void *d_proj, sgn_stream_t stream);
+
+/* out_feat: float4[S] = [alpha_s, r, g, b] for every work-list sample (samples without a valid
+ * neighbour are not written; the composite ignores them).  Optional (NULL to skip): out_blend
+ * float[S*K] = normalised weight * conf (the reference's `weight * conf_coefficient`), out_wnorm
+ * float[S*K] = normalised weight alone (the reference's `weight` output,
+ * point_aggregators.py:946-958).  stages: bit 0 = per-neighbour MLP + K-blend (writes alpha),
+ * bit 1 = colour MLP (rgb).  d_bpnet_f16 (SG, bpnet_dim > 0): sgn_bpnet_pack's table.
+ * d_point_proj: sgn_point_project's P, or NULL (block1.0 computed per row in full). */
+size_t sgn_aggregate_workspace_bytes(int64_t S);
+int sgn_aggregate(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f16, const void *d_point_proj,
+                  const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
+                  const void *d_packed_mlp, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
+                  void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream);
 
 /* ---- fp32-faithful aggregator (the reference's arithmetic) -------------------------
  * Same operator as sgn_point_project + sgn_aggregate (PointAggregator.forward / viewmlp,
@@ -214,31 +210,30 @@ int sgn_aggregate_sg(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpne
  * agree with an fp32 evaluation to a few fp32 ulps of sum |w x| per layer.  Hidden activations
  * must stay inside fp16 range (|x| < 65504): one outside it makes the sample's decoded features
  * non-finite, which the colour stage records in a flag of the workspace (never returned silently:
- * sgn_aggregate_check_f32 reports it).  bpnet_layers / bpnet_dim select the SG-NeRF
- * block2_bpnet variant as in sgn_mlp_pack_sg (0/0 = base ScanNet viewmlp).
- *   sgn_mlp_pack_f32        : 9 (+ block2_bpnet.0) layers as sgn_mlp_pack_sg -> blob of
- *                             sgn_mlp_packed_bytes_f32(bpnet_layers, bpnet_dim) bytes (0: unsupported)
+ * the caller reads the int32 at sgn_aggregate_flag_offset_f32; non-zero = a sample of the last
+ * colour stage run on this workspace had non-finite decoded features).
+ *   sgn_mlp_pack_f32        : the weights -> blob of sgn_mlp_packed_bytes_f32(bpnet_layers,
+ *                             bpnet_dim) bytes; sgn_mlp_pack_f32_host: the same into host memory
+ *                             (no device call; checkers)
  *   sgn_point_project_f32   : P[p] fp32, the block1.0 per-point part, followed by a packed 64-B
  *                             record per point (xyz, conf, colour, dir) that the row kernel gathers
  *                             as one cache line (sgn_point_proj_bytes_f32(N) bytes; pt->xyz, color,
- *                             dir, conf and embedding required; opaque to the caller)
- *   sgn_aggregate_f32       : as sgn_aggregate_sg (same outputs, stages bits), d_point_proj required;
+ *                             dir, conf and embedding required; opaque to the caller); d_idx /
+ *                             d_count as for sgn_point_project (a training step re-projects the
+ *                             rows its rays touch after each weight update instead of all N)
+ *   sgn_aggregate_f32       : as sgn_aggregate (same outputs, stages bits), d_point_proj required;
  *                             d_bpnet = fp32 [N, 96] BPNet point embedding when bpnet_dim = 96;
  *                             workspace sgn_aggregate_workspace_bytes_f32(S) (fp32 blended features
  *                             and the row kernel's paired-sample tables; opaque to the caller);
  *                             reads q->samp_nnb (valid neighbours are a prefix of each sample's K
  *                             slots, as sgn_query writes them); optional d_out_blend / d_out_wnorm are
  *                             zeroed by stage 1 before the valid rows are written
- *   sgn_aggregate_check_f32 : synchronises `stream` and returns -1 (sgn_last_error says why) when a
- *                             sample of the last colour stage run on this workspace had non-finite
- *                             decoded features (an activation outside fp16 range); 0 otherwise
- *   sgn_aggregate_flag_offset_f32 : byte offset of that int32 flag inside the workspace (for a
- *                             caller that reads it asynchronously, e.g. one frame later)
- *   sgn_aggregate_fs_offset_f32 (ABI 12) : byte offset inside the workspace of the blended features
- *                             f_s that stage 1 leaves for stage 2 -- fp32 [S_capacity][256], item i's
- *                             row at offset + 1024 i (a training step reads them) -- or -1 when a
- *                             workspace of workspace_bytes does not hold every item's row
- *   sgn_mlp_pack_f32_host   : sgn_mlp_pack_f32 into host memory (no device call; checkers)
+ *   sgn_aggregate_flag_offset_f32 : byte offset of the fp16-range flag inside the workspace (read it
+ *                             after the stream has run, e.g. one frame later)
+ *   sgn_aggregate_fs_offset_f32 : byte offset inside the workspace of the blended features f_s that
+ *                             stage 1 leaves for stage 2 -- fp32 [S_capacity][256], item i's row at
+ *                             offset + 1024 i (a training step reads them) -- or -1 when a workspace
+ *                             of workspace_bytes does not hold every item's row
  * 16-byte aligned device buffers. */
 size_t sgn_mlp_packed_bytes_f32(int32_t bpnet_layers, int32_t bpnet_dim);
 int sgn_mlp_pack_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
@@ -246,25 +241,45 @@ int sgn_mlp_pack_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *const
 int sgn_mlp_pack_f32_host(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
                           void *h_packed);
 size_t sgn_point_proj_bytes_f32(int64_t n_points);
-int sgn_point_project_f32(const sgn_point_tables *pt, const void *d_packed_mlp, void *d_proj, sgn_stream_t stream);
+int sgn_point_project_f32(const sgn_point_tables *pt, const void *d_packed_mlp, const int32_t *d_idx,
+                          const int64_t *d_count, void *d_proj, sgn_stream_t stream);
 size_t sgn_aggregate_workspace_bytes_f32(int64_t S);
 int sgn_aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const void *d_point_proj,
                       const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
                       const void *d_packed_mlp, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
                       void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream);
-int sgn_aggregate_check_f32(const void *d_workspace, size_t workspace_bytes, sgn_stream_t stream);
 size_t sgn_aggregate_flag_offset_f32(size_t workspace_bytes);
 int64_t sgn_aggregate_fs_offset_f32(size_t workspace_bytes, int64_t S_capacity);
 
-/* ---- plain-fp32 aggregator (ABI 16): the f32 mode's range fallback -----------------------
+/* fp32-faithful training forward (SURVEY §8 f1 at the reference's arithmetic): stage 1 of
+ * sgn_aggregate_f32 that also writes the pre-activations of block1.0 (d_z1), block1.2 (d_z2) and
+ * block3.0 (d_z3) (2^-s (W x + b), before LeakyReLU) as fp32 [S_capacity * K][256] at row s * K + k
+ * (the row's pidx index; rows without a neighbour are left unwritten), or, with d_row_off
+ * (sgn_train_lists), at the compact row d_row_off[s] + k.  d_zb (SG): block2_bpnet.0's
+ * pre-activations (block3.0's input), d_bpnet as for sgn_aggregate_f32.  The backward through them
+ * runs on sgn_x3_gemm and the row kernels below (train_hip, f32 mode).
+ *   sgn_mlp_layout_f32(0 / 1)   : bytes of the blob's fragment section / fp32 entries after it
+ *   sgn_mlp_pack_index_f32      : the blob as index maps, for packing it on the device from a flat
+ *                                 parameter: which 0 -> per fp16 element (layer << 20 | element)
+ *                                 (| 1 << 30 for the lo part, -1 padding); which 1 -> per fp32 entry
+ *                                 kind << 26 | layer << 20 | element (kinds: see mlp_x3.hip Y32Kind) */
+int sgn_aggregate_train_fwd_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
+                                const void *d_point_proj, const sgn_point_tables *pt, const sgn_query_out *q,
+                                int64_t S_capacity, int32_t K, const void *d_packed_mlp, float *d_out_feat,
+                                float *d_z1, float *d_z2, float *d_zb, float *d_z3, const int32_t *d_row_off,
+                                void *d_workspace, size_t workspace_bytes, sgn_stream_t stream);
+int64_t sgn_mlp_layout_f32(int32_t which);
+int sgn_mlp_pack_index_f32(int32_t bpnet_layers, int32_t bpnet_dim, int32_t which, int32_t *out, int64_t n);
+
+/* ---- plain-fp32 aggregator: the f32 mode's range fallback -----------------------
  * The same operator as sgn_aggregate_f32 (stages 1 + 2: alpha and colour of every work item,
  * optional blend / wnorm), every nn.Linear as v_mfma_f32_16x16x4_f32 on fp32 operands (exact fp32
  * products, fp32 sums) with the weights as the checkpoint holds them: no fp16 operand, so no range
- * limit below fp32's.  For frames whose activations leave fp16 range (sgn_aggregate_check_f32 /
- * the flag at sgn_aggregate_flag_offset_f32): the host re-runs them here instead of failing.  About
- * 1/5 of the split path's rate.  Needs no point projection (block1.0 is computed per row in full).
- *   sgn_mlp_pack_exact      : the 9 (+ block2_bpnet.0) layers in sgn_mlp_pack_f32's order -> fp32 blob of
- *                             sgn_mlp_packed_bytes_exact(bpnet_layers, bpnet_dim) bytes (W^T per layer)
+ * limit below fp32's.  For frames whose activations leave fp16 range (the flag at
+ * sgn_aggregate_flag_offset_f32): the host re-runs them here instead of failing.  About 1/5 of
+ * the split path's rate.  Needs no point projection (block1.0 is computed per row in full).
+ *   sgn_mlp_pack_exact      : the weights -> fp32 blob of sgn_mlp_packed_bytes_exact(bpnet_layers,
+ *                             bpnet_dim) bytes (W^T per layer)
  *   sgn_aggregate_exact     : workspace >= 1 KiB (1 KiB per work item of a chunk; a workspace holding
  *                             S_capacity items runs one chunk); d_bpnet fp32 [N, 96] when bpnet_dim = 96;
  *                             pt->pers / samp_pers optional as for sgn_aggregate_f32 */
@@ -276,42 +291,15 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
                         float *d_out_feat, float *d_out_blend, float *d_out_wnorm, void *d_workspace,
                         size_t workspace_bytes, sgn_stream_t stream);
 
-/* sgn_point_project_f32 for the points d_idx[0 .. *d_count) only (int32 indices < n_points; the
- * count is a device int64): a training step re-projects the rows its rays touch after each weight
- * update instead of all N.  The other points' P rows and records are left as they are. */
-int sgn_point_project_f32_subset(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
-                                 const int64_t *d_count, void *d_proj, sgn_stream_t stream);
-/* fp32-faithful training forward (SURVEY §8 f1 at the reference's arithmetic): stage 1 of
- * sgn_aggregate_f32 for the base viewmlp that also writes the pre-activations of block1.0, block1.2
- * and block3.0 (2^-s (W x + b), before LeakyReLU) as fp32 [S_capacity * K][256] at row s * K + k
- * (the row's pidx index; rows without a neighbour are left unwritten), or, with d_row_off
- * (sgn_train_lists), at the compact row d_row_off[s] + k.  The backward through them runs on
- * sgn_x3_gemm and the row kernels below (train_hip, f32 mode).
- *   sgn_mlp_layout_f32(0 / 1)   : bytes of the blob's fragment section / fp32 entries after it
- *   sgn_mlp_pack_index_f32      : the blob as index maps, for packing it on the device from a flat
- *                                 parameter: which 0 -> per fp16 element (layer << 20 | element)
- *                                 (| 1 << 30 for the lo part, -1 padding); which 1 -> per fp32 entry
- *                                 kind << 26 | layer << 20 | element (kinds: see mlp_x3.hip Y32Kind) */
-int sgn_aggregate_train_fwd_f32(const void *d_point_proj, const sgn_point_tables *pt, const sgn_query_out *q,
-                                int64_t S_capacity, int32_t K, const void *d_packed_mlp, float *d_out_feat,
-                                float *d_z1, float *d_z2, float *d_z3, const int32_t *d_row_off, void *d_workspace,
-                                size_t workspace_bytes, sgn_stream_t stream);
-/* The same for SG-NeRF's block2_bpnet.0 (point_aggregators.py:345-354, :629-636; bpnet_layers 1,
- * bpnet_dim 0 or 96 with d_bpnet the fp32 [N][96] BPNet embedding): d_z2 gets block1.2's
- * pre-activations, d_zb block2_bpnet.0's (block3.0's input).  d_packed_mlp: the SG fp32 blob. */
-int sgn_aggregate_train_fwd_f32_sg(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
-                                   const void *d_point_proj, const sgn_point_tables *pt, const sgn_query_out *q,
-                                   int64_t S_capacity, int32_t K, const void *d_packed_mlp, float *d_out_feat,
-                                   float *d_z1, float *d_z2, float *d_zb, float *d_z3, const int32_t *d_row_off,
-                                   void *d_workspace, size_t workspace_bytes, sgn_stream_t stream);
-int64_t sgn_mlp_layout_f32(int32_t which);
-int sgn_mlp_pack_index_f32(int32_t bpnet_layers, int32_t bpnet_dim, int32_t which, int32_t *out, int64_t n);
-
 /* ---- training: forward with saved activations + backward ---
- * Gradients of PointAggregator.forward / viewmlp (point_aggregators.py:868-959, :561-786)
- * and of the NeuralPoints gather (neural_points.py:942-988) -- the reference gets them from
- * torch autograd in optimize_parameters (base_rendering_model.py:534-664).  Base ScanNet
- * layout only (no block2_bpnet). Rows: row = 8 * item + k (item = work-list position). */
+ * Gradients of PointAggregator.forward / viewmlp (point_aggregators.py:868-959, :561-786) and of
+ * the NeuralPoints gather (neural_points.py:942-988) -- the reference gets them from torch autograd
+ * in optimize_parameters (base_rendering_model.py:534-664) -- on the fp16 blob of sgn_mlp_pack.
+ * Rows: row = 8 * item + k (item = work-list position).  SG: the forward additionally saves
+ * block2_bpnet's inputs (d_h2b, fp16 [rows][256], chain order) and saved->h2 then holds block3.0's
+ * inputs (block2_bpnet's output + the colour / dir channels); the backward writes block2_bpnet's
+ * scaled deltas (d_db, fp16 [rows][256]) and deltas->d2 = block1.2's.  The BPNet embedding is a
+ * detached input (neural_points.py:662): it gets no gradient. */
 typedef struct {
     void *x0;   /* fp16 [rows][288] block1.0 inputs           */
     void *h1;   /* fp16 [rows][256] block1.2 inputs           */
@@ -328,58 +316,39 @@ typedef struct {
     float *embedding, *color, *dir, *conf;  /* [N,32] [N,3] [N,3] [N]: accumulated (+=), unscaled */
 } sgn_point_grads;
 
-/* Stage 1 of sgn_aggregate in one launch (items [0, S_capacity)), saving per-row layer
- * inputs.  d_fs: fp16 [S_capacity][256] blended features (the colour MLP's input). */
-int sgn_aggregate_train_fwd(const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity,
-                            int32_t K, const void *d_packed_mlp, float *d_out_feat, void *d_fs,
-                            const sgn_agg_saved *saved, sgn_stream_t stream);
-/* Transposed-weight blob of block1.0, block1.2, block3.0, block3.2 (w[0..3] as in
- * sgn_mlp_pack), host in, device out (synchronous). */
+/* Stage 1 of sgn_aggregate in one launch (items [0, S_capacity)), saving per-row layer inputs.
+ * d_fs: fp16 [S_capacity][256] blended features (the colour MLP's input). */
+int sgn_aggregate_train_fwd(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f16,
+                            const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
+                            const void *d_packed_mlp, float *d_out_feat, void *d_fs, const sgn_agg_saved *saved,
+                            void *d_h2b, sgn_stream_t stream);
+/* Backward for n_items work items: d_dfs f32 [n_items][256], d_dalpha f32 [n_items] (d loss w.r.t.
+ * the blended features / alpha), d_scale: device scalar loss scale.  K: neighbours per sample of
+ * q->pidx, 1 .. 8, as in the forward. */
+int sgn_aggregate_backward(int32_t bpnet_layers, int32_t bpnet_dim, const sgn_point_tables *pt,
+                           const sgn_query_out *q, int32_t n_items, int32_t K, const void *d_packed_mlp,
+                           const void *d_tblob, const sgn_agg_saved *saved, const void *d_h2b, const float *d_dfs,
+                           const float *d_dalpha, const float *d_scale, const sgn_agg_deltas *deltas, void *d_db,
+                           const sgn_point_grads *grads, sgn_stream_t stream);
+/* Transposed-weight blob the backward reads: block1.0, block1.2, block3.0, block3.2 (w[0..3]) and,
+ * SG, the first 256 input columns of block2_bpnet.0 (w[4]).  Host in, device out (synchronous). */
 size_t sgn_train_tblob_bytes(void);
-int sgn_train_pack_t(const float *const *w, void *d_tblob, sgn_stream_t stream);
-/* Index maps for packing ON THE DEVICE from a flat fp32 parameter vector (the 9 base layers
- * in sgn_mlp_pack order, each weight row-major then its bias): out[i] = flat index + 1, 0 =
- * zero.  sgn_mlp_pack_index: which 0 = fp16 fragment part (n = OFF_F32 / 2 elements),
- * 1 = fp32 section (n = 2056); sgn_train_pack_index: transposed blob (n = tblob_bytes / 2). */
-int sgn_mlp_pack_index(int32_t which, int32_t *out, int64_t n);  /* which 2: split block1.0 sections */
-int sgn_train_pack_index(int32_t *out, int64_t n);
+int sgn_train_pack_t(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, void *d_tblob,
+                     sgn_stream_t stream);
+/* Index maps for packing both blobs ON THE DEVICE from the flat fp32 parameter vector: out[i] =
+ * flat index + 1, 0 = zero.  sgn_mlp_pack_index, by `which`:
+ *   0  fp16 fragment part           n = sgn_mlp_section(0) / 2 elements
+ *   1  fp32 section                 n = 2056
+ *   2  split block1.0 sections      n = (sgn_mlp_section(2) - sgn_mlp_section(1)) / 2
+ *   3  SG: block2_bpnet.0 fragments n = (packed_bytes - sgn_mlp_section(2) - 1024) / 2
+ *   4  SG: block2_bpnet.0 bias      n = 256 fp32
+ * (0 .. 2 are the same for every variant); sgn_train_pack_index: the transposed blob
+ * (n = sgn_train_tblob_bytes() / 2). */
+int sgn_mlp_pack_index(int32_t bpnet_layers, int32_t bpnet_dim, int32_t which, int32_t *out, int64_t n);
+int sgn_train_pack_index(int32_t bpnet_layers, int32_t bpnet_dim, int32_t *out, int64_t n);
 /* Column maps of the saved/delta tiles to reference indices (-1 = padding):
  * which 0: [256] chain order -> unit, 1: [288] -> block1.0 input, 2: [272] -> block3.0 input. */
 int sgn_train_colmap(int32_t which, int32_t *out, int32_t n);
-/* Backward for n_items work items: d_dfs f32 [n_items][256], d_dalpha f32 [n_items] (d loss
- * w.r.t. the blended features / alpha), d_scale: device scalar loss scale.  K (ABI 15): neighbours
- * per sample of q->pidx, 1 .. 8, as in the forward. */
-int sgn_aggregate_backward(const sgn_point_tables *pt, const sgn_query_out *q, int32_t n_items, int32_t K,
-                           const void *d_packed_mlp, const void *d_tblob, const sgn_agg_saved *saved,
-                           const float *d_dfs, const float *d_dalpha, const float *d_scale,
-                           const sgn_agg_deltas *deltas, const sgn_point_grads *grads,
-                           sgn_stream_t stream);
-
-/* ---- training of the SG-NeRF variant (block2_bpnet, point_aggregators.py:345-354, :629-636) ----
- * Gradients of block2_bpnet.0 = Linear(256 + bpnet_dim -> 256) + LReLU between block1 and
- * block3, on the fp16 blob of sgn_mlp_pack_sg (bpnet_layers 1, bpnet_dim 0 or 96; 0 layers =
- * the base functions).  The forward additionally saves block2_bpnet's inputs h (d_h2b, fp16
- * [rows][256], chain order) and saved->h2 holds block3.0's inputs (block2_bpnet's output + the
- * colour / dir channels); the backward writes block2_bpnet's scaled deltas (d_db, fp16
- * [rows][256]) and deltas->d2 = block1.2's.  The BPNet embedding is a detached input
- * (neural_points.py:662): it gets no gradient.  The transposed blob gains block2_bpnet.0's
- * first 256 input columns (sgn_train_pack_t_sg, w[0..3] and w[4] = block2_bpnet.0's weight). */
-int sgn_aggregate_train_fwd_sg(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f16,
-                               const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
-                               const void *d_packed_mlp, float *d_out_feat, void *d_fs, const sgn_agg_saved *saved,
-                               void *d_h2b, sgn_stream_t stream);
-int sgn_aggregate_backward_sg(int32_t bpnet_layers, int32_t bpnet_dim, const sgn_point_tables *pt,
-                              const sgn_query_out *q, int32_t n_items, int32_t K, const void *d_packed_mlp,
-                              const void *d_tblob,
-                              const sgn_agg_saved *saved, const void *d_h2b, const float *d_dfs, const float *d_dalpha,
-                              const float *d_scale, const sgn_agg_deltas *deltas, void *d_db,
-                              const sgn_point_grads *grads, sgn_stream_t stream);
-int sgn_train_pack_t_sg(const float *const *w, int32_t bpnet_dim, void *d_tblob, sgn_stream_t stream);
-/* Index maps over the SG flat vector (the 9 base layers, then block2_bpnet.0 weight and bias):
- * sgn_mlp_pack_index_sg which 3 = block2_bpnet fragments (n = (bias offset - OFF_WB) / 2 fp16
- * elements), 4 = its bias (n = 256 fp32); sgn_train_pack_index_sg = the transposed blob. */
-int sgn_mlp_pack_index_sg(int32_t bpnet_layers, int32_t bpnet_dim, int32_t which, int32_t *out, int64_t n);
-int sgn_train_pack_index_sg(int32_t bpnet_dim, int32_t *out, int64_t n);
 
 /* ---- training: point-parameter Adam and bias-gradient column sums ------------------
  * Replaces torch.optim.Adam.step for the neural-point group (the reference's optimizer,
@@ -415,7 +384,7 @@ int sgn_adam_step_multi(int32_t n_t, float *const *d_param, float *const *d_grad
  * + 1, n_rows)) bytes receiving list 1's distinct valid rows and row 0 -- int64 count at [0], the
  * number of list-1 ids >= n_rows at [1] (a query / table mismatch), int32 rows from byte 16.
  * mv_stride (host, optional): row stride in floats of d_exp_avg[t] / d_exp_avg_sq[t] (>= row_width[t];
- * null: row_width) -- the narrow tensors' moments may share one packed [n_rows][16] buffer (ABI 18). */
+ * null: row_width) -- the narrow tensors' moments may share one packed [n_rows][16] buffer. */
 size_t sgn_adam_rows_workspace_bytes(int64_t n_entries);
 size_t sgn_adam_rows_pend_bytes(int64_t n_entries);
 int sgn_adam_rows(int32_t n_t, float *const *d_param, float *const *d_grad, float *const *d_exp_avg,
@@ -437,7 +406,7 @@ int sgn_colsum_f16(int32_t count, const void *const *d_x, int64_t rows, int32_t 
  * dza^T h4 (point_aggregators.py:650-653, nn.Linear(256, 1)) in the bias sums' launch. */
 int sgn_colsum_f16_weighted(int32_t count, const void *const *d_x, const float *const *d_rw, int64_t rows,
                             int32_t cols, float *d_ws, float *d_out, sgn_stream_t stream);
-/* ABI 14: the same sums left as SGN_COLSUM_SLABS fixed row-slab partials in d_ws (one launch, no final
+/* The same sums left as SGN_COLSUM_SLABS fixed row-slab partials in d_ws (one launch, no final
  * pass), for sgn_grad_accumulate to add: column c of matrix i, slab b at
  * d_ws[(i * SGN_COLSUM_SLABS + b) * 256 + c]; for weighted matrices the slab's sum of the row weights
  * (the alpha branch's bias gradient sum(dza), point_aggregators.py:650-653) at
@@ -517,15 +486,15 @@ int sgn_pow2_scale(const float *d_a, int64_t na, const float *d_b, int64_t nb, v
  * neighbour slots, train.composite_losses) and every neighbour d_pidx[e] >= 0, e < d_counters[0] * K
  * (sgn_query's sample count; s_cap bounds it).  Appends them to d_idx (int32 [n_points]) in no
  * particular order and writes their count to d_count2[step & 1]; d_count2[(step + 1) & 1] is
- * cleared for the next step; d_count2[2] (ABI 12) accumulates the neighbour indices >= n_points met
+ * cleared for the next step; d_count2[2] accumulates the neighbour indices >= n_points met
  * (a query / point-table mismatch: such a point is never projected), so a caller can assert it is 0.  d_stamp: int32 [n_points], -1 once at allocation, then owned by the
  * caller's step counter (step >= 0, increasing).  Replaces the torch touched_rows mask / scan /
- * scatter (train.py) on the single-GPU fp32 step's projection subset (sgn_point_project_f32_subset);
+ * scatter (train.py) on the single-GPU fp32 step's projection subset (sgn_point_project_f32's d_idx);
  * the neighbours come from the reference's query (neural_points.py:942-988). */
 int sgn_touched_points(const int32_t *d_pidx, const int32_t *d_counters, int64_t s_cap, int32_t K, int64_t n_points,
                        int32_t step, int32_t *d_stamp, int32_t *d_idx, int64_t *d_count2, sgn_stream_t stream);
 
-/* The distinct points a render frame's samples name (ABI 19), for sgn_point_project_f32_subset: the
+/* The distinct points a render frame's samples name, for sgn_point_project(_f32)'s d_idx: the
  * block1.0 projection then runs over those points only (~19 % of the 1.2 M points of a config-2
  * frame) instead of all of them.  Point 0 and every neighbour d_pidx[e] >= 0, e < min(d_counters[0]
  * * K, s_cap * K), go to d_idx (int32 [n_points], no particular order) with their count at
@@ -536,7 +505,7 @@ size_t sgn_frame_points_mark_bytes(int64_t n_points);
 int sgn_frame_points(const int32_t *d_pidx, const int32_t *d_counters, int64_t s_cap, int32_t K, int64_t n_points,
                      uint8_t *d_mark, int32_t *d_idx, int64_t *d_count, sgn_stream_t stream);
 
-/* ---- fp32 training step on hand-written kernels (ABI 9; SG entries ABI 10) -----------------------------------
+/* ---- fp32 training step on hand-written kernels -----------------------------------
  * The reference's fp32 autograd through PointAggregator / viewmlp and the NeuralPoints gather
  * (models/aggregators/point_aggregators.py:561-786, :868-959; neural_points.py:942-988; run from
  * optimize_parameters, base_rendering_model.py:534-664, mvs_points_volumetric_model.py:116-141) as
@@ -583,14 +552,14 @@ typedef struct {
     int32_t splits;
     int32_t products;   /* 3 (or 0): hi/lo products, fp32 accuracy; 1: the hi halves only (fp16 operands,
                            the f16 training step's colour MLP; colour-layer shapes only) */
-    void *bpack;        /* ABI 13, mode 0: NULL, or a 16-B aligned workspace of sgn_x3_gemm_bpack_bytes(g)
+    void *bpack;        /* mode 0: NULL, or a 16-B aligned workspace of sgn_x3_gemm_bpack_bytes(g)
                            bytes: the weight blocks are split there once per call (one extra launch) and
                            every workgroup copies its block into LDS by DMA instead of converting it */
 } sgn_x3_gemm_args;
 int sgn_x3_gemm(const sgn_x3_gemm_args *g, sgn_stream_t stream);
-size_t sgn_x3_gemm_bpack_bytes(const sgn_x3_gemm_args *g);   /* ABI 13; 0 unless mode 0 with K <= 288 */
+size_t sgn_x3_gemm_bpack_bytes(const sgn_x3_gemm_args *g);   /* 0 unless mode 0 with K <= 288 */
 
-/* The f16 training step's row-layer weight gradients (ABI 13; replaces the fp16 GEMMs of the
+/* The f16 training step's row-layer weight gradients (replaces the fp16 GEMMs of the
  * reference's autograd dW of the aggregator MLP, point_aggregators.py:868-959 under
  * base_rendering_model.py:534-664): part[s][m][n] = sum over the rows r of run s of d[r][m] x[r][n]
  * (fp32 accumulation of the exact fp16 products) for m < 256, n < ncols, the rows r < n_rows cut into
@@ -694,7 +663,7 @@ typedef struct {
     float bg[3];
     float zero_one_weight;     /* 1e-4 (train_ft) */
     float zero_one_eps;        /* 1e-3 */
-    const float *bg_ray;       /* ABI 16: device float[R*3], the rays' background (inputs['bg_ray'] of the
+    const float *bg_ray;       /* device float[R*3], the rays' background (inputs['bg_ray'] of the
                                   plane background model, fill_invalid's T_bg * bg_ray,
                                   neural_points_volumetric_model.py:175-177); NULL: bg[3] for every ray */
 } sgn_loss_params;

@@ -12,7 +12,7 @@ import torch  # noqa: F401  -- loads torch's libamdhip64 first so the .so binds 
 
 # SGN_HIP_LIB: another build of the same ABI (same-box A/B of kernel variants, tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SGN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsgn_hip.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 COLSUM_SLABS = 512   # SGN_COLSUM_SLABS
 
 c_i32, c_i64, c_u64, c_f32, c_vp, c_sz = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
@@ -107,37 +107,25 @@ SIGNATURES = {
     "sgn_query_workspace_bytes": (c_sz, [c_i64]),
     "sgn_query": (c_i32, [c_vp, ctypes.POINTER(QueryParams), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
                           ctypes.POINTER(QueryOut), c_vp, c_sz, c_vp]),
-    "sgn_mlp_packed_bytes": (c_sz, []),
-    "sgn_mlp_pack": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp]),
+    "sgn_mlp_packed_bytes": (c_sz, [c_i32, c_i32]),
+    "sgn_mlp_pack": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp]),
     "sgn_aggregate_workspace_bytes": (c_sz, [c_i64]),
-    "sgn_aggregate": (c_i32, [ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64, c_i32,
-                              c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_i32, c_vp]),
-    "sgn_mlp_packed_bytes_sg": (c_sz, [c_i32, c_i32]),
-    "sgn_mlp_pack_sg": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp]),
+    "sgn_aggregate": (c_i32, [c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64,
+                              c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_i32, c_vp]),
     "sgn_bpnet_pack": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
     "sgn_point_proj_bytes": (c_sz, [c_i64]),
-    "sgn_point_project": (c_i32, [ctypes.POINTER(PointTables), c_vp, c_vp, c_vp]),
+    "sgn_point_project": (c_i32, [ctypes.POINTER(PointTables), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgn_mlp_section": (c_sz, [c_i32]),
-    "sgn_aggregate_sg": (c_i32, [c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64,
-                                 c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_i32, c_vp]),
-    "sgn_aggregate_train_fwd": (c_i32, [ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64, c_i32, c_vp,
-                                        c_vp, c_vp, ctypes.POINTER(AggSaved), c_vp]),
+    "sgn_aggregate_train_fwd": (c_i32, [c_i32, c_i32, c_vp, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut),
+                                        c_i64, c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(AggSaved), c_vp, c_vp]),
     "sgn_train_tblob_bytes": (c_sz, []),
-    "sgn_train_pack_t": (c_i32, [ctypes.POINTER(c_vp), c_vp, c_vp]),
-    "sgn_mlp_pack_index": (c_i32, [c_i32, ctypes.POINTER(c_i32), c_i64]),
-    "sgn_train_pack_index": (c_i32, [ctypes.POINTER(c_i32), c_i64]),
+    "sgn_train_pack_t": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_vp), c_vp, c_vp]),
+    "sgn_mlp_pack_index": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_i64]),
+    "sgn_train_pack_index": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_i32), c_i64]),
     "sgn_train_colmap": (c_i32, [c_i32, ctypes.POINTER(c_i32), c_i32]),
-    "sgn_aggregate_backward": (c_i32, [ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i32, c_i32, c_vp, c_vp,
-                                       ctypes.POINTER(AggSaved), c_vp, c_vp, c_vp, ctypes.POINTER(AggDeltas),
-                                       ctypes.POINTER(PointGrads), c_vp]),
-    "sgn_aggregate_train_fwd_sg": (c_i32, [c_i32, c_i32, c_vp, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut),
-                                           c_i64, c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(AggSaved), c_vp, c_vp]),
-    "sgn_aggregate_backward_sg": (c_i32, [c_i32, c_i32, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i32,
-                                          c_i32, c_vp, c_vp, ctypes.POINTER(AggSaved), c_vp, c_vp, c_vp, c_vp,
-                                          ctypes.POINTER(AggDeltas), c_vp, ctypes.POINTER(PointGrads), c_vp]),
-    "sgn_train_pack_t_sg": (c_i32, [ctypes.POINTER(c_vp), c_i32, c_vp, c_vp]),
-    "sgn_mlp_pack_index_sg": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_i64]),
-    "sgn_train_pack_index_sg": (c_i32, [c_i32, ctypes.POINTER(c_i32), c_i64]),
+    "sgn_aggregate_backward": (c_i32, [c_i32, c_i32, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i32,
+                                       c_i32, c_vp, c_vp, ctypes.POINTER(AggSaved), c_vp, c_vp, c_vp, c_vp,
+                                       ctypes.POINTER(AggDeltas), c_vp, ctypes.POINTER(PointGrads), c_vp]),
     "sgn_adam_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, c_i64, c_i32, c_vp]),
     "sgn_adam_step_multi": (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
@@ -151,7 +139,6 @@ SIGNATURES = {
                               c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp, c_sz, c_vp,
                               ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_i32, c_i32,
                               c_vp]),
-    "sgn_point_project_subset": (c_i32, [ctypes.POINTER(PointTables), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgn_frame_points_mark_bytes": (c_sz, [c_i64]),
     "sgn_frame_points": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "sgn_colsum_workspace_bytes": (c_sz, [c_i32]),
@@ -175,23 +162,19 @@ SIGNATURES = {
     "sgn_mlp_pack_f32": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp]),
     "sgn_mlp_pack_f32_host": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "sgn_point_proj_bytes_f32": (c_sz, [c_i64]),
-    "sgn_point_project_f32": (c_i32, [ctypes.POINTER(PointTables), c_vp, c_vp, c_vp]),
-    "sgn_point_project_f32_subset": (c_i32, [ctypes.POINTER(PointTables), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgn_point_project_f32": (c_i32, [ctypes.POINTER(PointTables), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgn_aggregate_workspace_bytes_f32": (c_sz, [c_i64]),
     "sgn_aggregate_f32": (c_i32, [c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64, c_i32, c_vp,
                                   c_vp, c_vp, c_vp, c_vp, c_sz, c_i32, c_vp]),
-    "sgn_aggregate_check_f32": (c_i32, [c_vp, c_sz, c_vp]),
     "sgn_mlp_packed_bytes_exact": (c_sz, [c_i32, c_i32]),
     "sgn_mlp_pack_exact": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp]),
     "sgn_aggregate_exact": (c_i32, [c_i32, c_i32, c_vp, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64,
                                     c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "sgn_aggregate_flag_offset_f32": (c_sz, [c_sz]),
     "sgn_aggregate_fs_offset_f32": (c_i64, [c_sz, c_i64]),
-    "sgn_aggregate_train_fwd_f32": (c_i32, [c_vp, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64, c_i32,
-                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "sgn_aggregate_train_fwd_f32_sg": (c_i32, [c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(PointTables),
-                                               ctypes.POINTER(QueryOut), c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                               c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "sgn_aggregate_train_fwd_f32": (c_i32, [c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(PointTables),
+                                            ctypes.POINTER(QueryOut), c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp, c_sz, c_vp]),
     "sgn_train_row_gather": (c_i32, [ctypes.POINTER(QueryOut), c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "sgn_x3_gemm": (c_i32, [ctypes.POINTER(X3GemmArgs), c_vp]),
     "sgn_x3_gemm_bpack_bytes": (c_sz, [ctypes.POINTER(X3GemmArgs)]),

@@ -124,6 +124,16 @@ struct AggArgs {
     int32_t K;
 };
 
+// host: the fields every entry point fills the same way (pers / samp_pers are the caller's business:
+// the training entries take none)
+inline void fill_agg_args(AggArgs &a, const sgn_point_tables *pt, const sgn_query_out *q, int32_t K) {
+    a.xyz = pt->xyz; a.emb = pt->embedding; a.color = pt->color; a.dir = pt->dir; a.conf = pt->conf;
+    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
+    a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
+    a.samp_locw = q->samp_locw;
+    a.K = K;
+}
+
 // training save: one 16-byte fragment of a 32-row tile -> [rows][C] (C multiple of 16)
 __device__ __forceinline__ void save_frag(_Float16 *base, int C, int64_t row0, int s, h8 v, int lane, bool ok) {
     if (ok) *(h8 *)(base + (row0 + (lane & 31)) * C + s * 16 + (lane >> 5) * 8) = v;

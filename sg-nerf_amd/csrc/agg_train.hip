@@ -545,68 +545,28 @@ extern "C" {
 size_t sgn_train_tblob_bytes(void) { return sgn::T_BYTES; }
 
 /* Index map of the transposed blob over the flat parameter vector (as sgn_mlp_pack_index):
- * n = sgn_train_tblob_bytes() / 2 elements, value = flat index + 1, 0 = zero. */
-int sgn_train_pack_index(int32_t *out, int64_t n) {
+ * n = sgn_train_tblob_bytes() / 2 elements, value = flat index + 1, 0 = zero.  SG: the
+ * block2_bpnet section maps too (block2_bpnet.0's first 256 input columns). */
+int sgn_train_pack_index(int32_t bpnet_layers, int32_t bpnet_dim, int32_t *out, int64_t n) {
     using namespace sgn;
+    const int ksb = mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
     SGN_REQUIRE(out && n == (int64_t)(T_BYTES / 2), "sgn_train_pack_index: bad size");
-    // flat offsets of block1.0 / block1.2 / block3.0 / block3.2 weights (LAYERS order: w, b per layer)
-    const int64_t o0 = 0, o1 = o0 + 256 * 284 + 256, o2 = o1 + 256 * 256 + 256, o3 = o2 + 256 * 263 + 256;
-    const int64_t offs[4] = {o0, o1, o2, o3};
-    const int sz[4] = {256 * 284, 256 * 256, 256 * 263, 256 * 256};
-    std::vector<std::vector<float>> wi(4);
-    std::vector<const float *> wp(4);
-    for (int L = 0; L < 4; ++L) {
-        wi[L].resize(sz[L]);
-        for (int i = 0; i < sz[L]; ++i) wi[L][i] = (float)(offs[L] + i + 1);
-        wp[L] = wi[L].data();
-    }
+    const mlp::IndexWeights iw(ksb, bpnet_dim);
     std::vector<float> e(T_BYTES / 2, 0.f);
-    pack_tblob(wp.data(), e.data());
+    pack_tblob(iw.wp.data(), e.data(), ksb > 0 ? iw.wp[9] : nullptr, bpnet_dim);
     for (int64_t i = 0; i < n; ++i) out[i] = (int32_t)e[(size_t)i];
     return 0;
 }
 
-/* As sgn_train_pack_index for the SG flat vector (the 9 base layers, then block2_bpnet.0 weight
- * [256][256 + bpnet_dim] and bias): the block2_bpnet section of the transposed blob maps too. */
-int sgn_train_pack_index_sg(int32_t bpnet_dim, int32_t *out, int64_t n) {
+int sgn_train_pack_t(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, void *d_tblob,
+                     sgn_stream_t stream) {
     using namespace sgn;
-    SGN_REQUIRE(bpnet_dim == 0 || bpnet_dim == mlp::BP_DIM, "bpnet_dim must be 0 or 96");
-    SGN_REQUIRE(out && n == (int64_t)(T_BYTES / 2), "sgn_train_pack_index_sg: bad size");
-    const int64_t o0 = 0, o1 = o0 + 256 * 284 + 256, o2 = o1 + 256 * 256 + 256, o3 = o2 + 256 * 263 + 256;
-    const int64_t ob = 341764;  // after the 9 base layers (weights.N_PARAMS)
-    const int64_t offs[5] = {o0, o1, o2, o3, ob};
-    const int64_t sz[5] = {256 * 284, 256 * 256, 256 * 263, 256 * 256, (int64_t)256 * (256 + bpnet_dim)};
-    std::vector<std::vector<float>> wi(5);
-    std::vector<const float *> wp(5);
-    for (int L = 0; L < 5; ++L) {
-        wi[L].resize((size_t)sz[L]);
-        for (int64_t i = 0; i < sz[L]; ++i) wi[L][(size_t)i] = (float)(offs[L] + i + 1);
-        wp[L] = wi[L].data();
-    }
-    std::vector<float> e(T_BYTES / 2, 0.f);
-    pack_tblob(wp.data(), e.data(), wp[4], bpnet_dim);
-    for (int64_t i = 0; i < n; ++i) out[i] = (int32_t)e[(size_t)i];
-    return 0;
-}
-
-int sgn_train_pack_t_sg(const float *const *w, int32_t bpnet_dim, void *d_tblob, sgn_stream_t stream) {
-    using namespace sgn;
-    SGN_REQUIRE(w && w[0] && w[1] && w[2] && w[3] && w[4], "null weights");
-    SGN_REQUIRE(bpnet_dim == 0 || bpnet_dim == mlp::BP_DIM, "bpnet_dim must be 0 or 96");
+    const int ksb = mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
+    SGN_REQUIRE(w && w[0] && w[1] && w[2] && w[3] && (ksb == 0 || w[4]), "null weights");
     std::vector<uint8_t> blob(T_BYTES, 0);
-    pack_tblob(w, (_Float16 *)blob.data(), w[4], bpnet_dim);
-    hipStream_t st = as_stream(stream);
-    SGN_CHECK_HIP(hipMemcpyAsync(d_tblob, blob.data(), T_BYTES, hipMemcpyHostToDevice, st));
-    SGN_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-
-int sgn_train_pack_t(const float *const *w, void *d_tblob, sgn_stream_t stream) {
-    using namespace sgn;
-    using namespace sgn::mlp;
-    SGN_REQUIRE(w && w[0] && w[1] && w[2] && w[3], "null weights");
-    std::vector<uint8_t> blob(T_BYTES, 0);
-    pack_tblob(w, (_Float16 *)blob.data());
+    pack_tblob(w, (_Float16 *)blob.data(), ksb > 0 ? w[4] : nullptr, bpnet_dim);
     hipStream_t st = as_stream(stream);
     SGN_CHECK_HIP(hipMemcpyAsync(d_tblob, blob.data(), T_BYTES, hipMemcpyHostToDevice, st));
     SGN_CHECK_HIP(hipStreamSynchronize(st));
@@ -629,12 +589,16 @@ int sgn_train_colmap(int32_t which, int32_t *out, int32_t n) {
     return 0;
 }
 
-int sgn_aggregate_backward(const sgn_point_tables *pt, const sgn_query_out *q, int32_t n_items, int32_t K,
-                           const void *d_packed, const void *d_tblob, const sgn_agg_saved *saved,
-                           const float *d_dfs, const float *d_dalpha, const float *d_scale,
-                           const sgn_agg_deltas *deltas, const sgn_point_grads *grads, sgn_stream_t stream) {
+int sgn_aggregate_backward(int32_t bpnet_layers, int32_t bpnet_dim, const sgn_point_tables *pt,
+                           const sgn_query_out *q, int32_t n_items, int32_t K, const void *d_packed,
+                           const void *d_tblob, const sgn_agg_saved *saved, const void *d_h2b, const float *d_dfs,
+                           const float *d_dalpha, const float *d_scale, const sgn_agg_deltas *deltas, void *d_db,
+                           const sgn_point_grads *grads, sgn_stream_t stream) {
     using namespace sgn;
-    SGN_REQUIRE(pt && q && d_packed && d_tblob && saved && deltas && grads && d_scale, "null argument");
+    const int ksb = mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
+    SGN_REQUIRE(pt && q && d_packed && d_tblob && saved && deltas && grads && d_scale && (ksb == 0 || (d_h2b && d_db)),
+                "null argument");
     SGN_REQUIRE(n_items >= 0, "n_items < 0");
     SGN_REQUIRE(K >= 1 && K <= 8, "the MFMA aggregator takes K = 1 .. 8 neighbours per sample");
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir && !pt->pers, "camera required, no precomputed pers");
@@ -643,17 +607,14 @@ int sgn_aggregate_backward(const sgn_point_tables *pt, const sgn_query_out *q, i
     SGN_REQUIRE(deltas->d1 && deltas->d2 && deltas->d3 && deltas->d4 && deltas->h4 && deltas->dza, "null delta outputs");
     SGN_REQUIRE(grads->embedding && grads->color && grads->dir && grads->conf, "null gradient outputs");
     BwdArgs b{};
-    AggArgs &a = b.a;
-    a.xyz = pt->xyz; a.emb = pt->embedding; a.color = pt->color; a.dir = pt->dir; a.conf = pt->conf;
-    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
-    a.pers = nullptr; a.samp_pers = nullptr;
-    a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
-    a.samp_locw = q->samp_locw;
-    a.K = K;
-    a.blob = d_packed; a.blob_bytes = mlp::TOTAL_BYTES;
-    a.blend = nullptr; a.wnorm = nullptr;
+    fill_agg_args(b.a, pt, q, K);
+    b.a.blob = d_packed; b.a.blob_bytes = mlp::total_bytes_sg(ksb);
     b.tblob = d_tblob;
     b.sh1 = (const _Float16 *)saved->h1; b.sh2 = (const _Float16 *)saved->h2; b.sh3 = (const _Float16 *)saved->h3;
+    if (ksb > 0) {
+        b.sh2b = (const _Float16 *)d_h2b;
+        b.db = (_Float16 *)d_db;
+    }
     b.dfs = d_dfs; b.dalpha = d_dalpha; b.scale = d_scale;
     b.d4 = (_Float16 *)deltas->d4; b.d3 = (_Float16 *)deltas->d3; b.d2 = (_Float16 *)deltas->d2;
     b.d1 = (_Float16 *)deltas->d1; b.h4 = (_Float16 *)deltas->h4; b.dza = deltas->dza;
@@ -661,53 +622,8 @@ int sgn_aggregate_backward(const sgn_point_tables *pt, const sgn_query_out *q, i
     b.n_items = n_items;
     const int64_t waves = ((int64_t)n_items + 3) / 4;
     const int64_t blocks = (waves + 3) / 4;
-    hipLaunchKernelGGL(k_agg_bwd<false>, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(BWD_TPB), 0,
-                       as_stream(stream), b);
-    SGN_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int sgn_aggregate_backward_sg(int32_t bpnet_layers, int32_t bpnet_dim, const sgn_point_tables *pt,
-                              const sgn_query_out *q, int32_t n_items, int32_t K, const void *d_packed,
-                              const void *d_tblob,
-                              const sgn_agg_saved *saved, const void *d_h2b, const float *d_dfs, const float *d_dalpha,
-                              const float *d_scale, const sgn_agg_deltas *deltas, void *d_db,
-                              const sgn_point_grads *grads, sgn_stream_t stream) {
-    using namespace sgn;
-    if (bpnet_layers == 0)
-        return sgn_aggregate_backward(pt, q, n_items, K, d_packed, d_tblob, saved, d_dfs, d_dalpha, d_scale, deltas,
-                                      grads, stream);
-    SGN_REQUIRE(bpnet_layers == 1 && (bpnet_dim == 0 || bpnet_dim == mlp::BP_DIM),
-                "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
-    SGN_REQUIRE(pt && q && d_packed && d_tblob && saved && deltas && grads && d_scale && d_h2b && d_db, "null argument");
-    SGN_REQUIRE(n_items >= 0, "n_items < 0");
-    SGN_REQUIRE(K >= 1 && K <= 8, "the MFMA aggregator takes K = 1 .. 8 neighbours per sample");
-    SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir && !pt->pers, "camera required, no precomputed pers");
-    if (n_items == 0) return 0;
-    SGN_REQUIRE(d_dfs && d_dalpha && saved->h1 && saved->h2 && saved->h3, "null saved/input tensors");
-    SGN_REQUIRE(deltas->d1 && deltas->d2 && deltas->d3 && deltas->d4 && deltas->h4 && deltas->dza, "null delta outputs");
-    SGN_REQUIRE(grads->embedding && grads->color && grads->dir && grads->conf, "null gradient outputs");
-    BwdArgs b{};
-    AggArgs &a = b.a;
-    a.xyz = pt->xyz; a.emb = pt->embedding; a.color = pt->color; a.dir = pt->dir; a.conf = pt->conf;
-    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
-    a.pers = nullptr; a.samp_pers = nullptr;
-    a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
-    a.samp_locw = q->samp_locw;
-    a.K = K;
-    a.blob = d_packed; a.blob_bytes = mlp::total_bytes_sg(mlp::ks_bp(bpnet_dim));
-    a.blend = nullptr; a.wnorm = nullptr;
-    b.tblob = d_tblob;
-    b.sh1 = (const _Float16 *)saved->h1; b.sh2 = (const _Float16 *)saved->h2; b.sh3 = (const _Float16 *)saved->h3;
-    b.sh2b = (const _Float16 *)d_h2b; b.db = (_Float16 *)d_db;
-    b.dfs = d_dfs; b.dalpha = d_dalpha; b.scale = d_scale;
-    b.d4 = (_Float16 *)deltas->d4; b.d3 = (_Float16 *)deltas->d3; b.d2 = (_Float16 *)deltas->d2;
-    b.d1 = (_Float16 *)deltas->d1; b.h4 = (_Float16 *)deltas->h4; b.dza = deltas->dza;
-    b.g_emb = grads->embedding; b.g_color = grads->color; b.g_dir = grads->dir; b.g_conf = grads->conf;
-    b.n_items = n_items;
-    const int64_t waves = ((int64_t)n_items + 3) / 4;
-    const int64_t blocks = (waves + 3) / 4;
-    hipLaunchKernelGGL(k_agg_bwd<true>, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(BWD_TPB), 0,
+    auto kern = ksb == 0 ? k_agg_bwd<false> : k_agg_bwd<true>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(BWD_TPB), 0,
                        as_stream(stream), b);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;

@@ -3,7 +3,7 @@
 //
 // The fast fp32-faithful kernels (mlp_x3.hip) carry every activation as an fp16 (hi, lo) pair, so
 // an activation with |x| >= 65504 cannot be represented there; k_color16 flags such a frame
-// (counters / sgn_aggregate_check_f32).  The reference has no such limit: nn.Linear in fp32
+// (the workspace word at sgn_aggregate_flag_offset_f32).  The reference has no such limit: nn.Linear in fp32
 // (point_aggregators.py:561-786 viewmlp, :868-959 forward).  The host re-runs a flagged frame's
 // aggregation here: the same gather, dists, weights and K-blend, every nn.Linear as fp32 MFMAs
 // with fp32 operands (each MFMA a k-ordered fmaf chain: exact fp32 products, fp32 sums) on the
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(TPB, 1) void k_color_exact(XArgs xa) {
 extern "C" {
 
 size_t sgn_mlp_packed_bytes_exact(int32_t bpnet_layers, int32_t bpnet_dim) {
-    if (!(bpnet_layers == 0 || (bpnet_layers == 1 && (bpnet_dim == 0 || bpnet_dim == 96)))) return 0;
+    if (sgn::mlp::variant_ksb(bpnet_layers, bpnet_dim) < 0) return 0;
     return (size_t)sgn::xe::x_layout(bpnet_layers, bpnet_dim).floats * 4;
 }
 
@@ -413,8 +413,7 @@ int sgn_mlp_pack_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *con
     using namespace sgn;
     using namespace sgn::xe;
     SGN_REQUIRE(w && b && d_packed, "null argument");
-    SGN_REQUIRE(bpnet_layers == 0 || (bpnet_layers == 1 && (bpnet_dim == 0 || bpnet_dim == 96)),
-                "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
+    SGN_REQUIRE_VARIANT(variant_ksb(bpnet_layers, bpnet_dim));
     const XLayout ly = x_layout(bpnet_layers, bpnet_dim);
     const int src[NL] = {0, 1, 9, 2, 3, 4, 5, 6, 7, 8};  // x_layout layer -> argument index
     std::vector<float> blob(ly.floats, 0.f);
@@ -445,8 +444,7 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
     using namespace sgn;
     using namespace sgn::xe;
     SGN_REQUIRE(pt && q && d_packed_exact && d_out_feat && d_workspace, "null argument");
-    SGN_REQUIRE(bpnet_layers == 0 || (bpnet_layers == 1 && (bpnet_dim == 0 || bpnet_dim == 96)),
-                "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
+    SGN_REQUIRE_VARIANT(variant_ksb(bpnet_layers, bpnet_dim));
     SGN_REQUIRE(bpnet_dim == 0 || (d_bpnet && ((uintptr_t)d_bpnet & 15) == 0),
                 "bpnet_dim > 0 needs the 16-byte aligned fp32 BPNet point embedding");
     SGN_REQUIRE(K >= 1 && K <= 8, "the aggregator takes K = 1 .. 8 neighbours per sample");
@@ -463,12 +461,8 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
     if (S_capacity == 0 || pt->n_points == 0) return 0;  // no neighbours: no work item
     XArgs x{};
     AggArgs &a = x.a;
-    a.xyz = pt->xyz; a.emb = pt->embedding; a.color = pt->color; a.dir = pt->dir; a.conf = pt->conf;
-    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
+    fill_agg_args(a, pt, q, K);
     a.pers = pt->pers; a.samp_pers = pt->samp_pers;
-    a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
-    a.samp_locw = q->samp_locw;
-    a.K = K;
     a.bpnet32 = d_bpnet;
     a.feat = d_out_feat; a.blend = d_out_blend; a.wnorm = d_out_wnorm;
     x.w = (const float *)d_packed_exact;

@@ -852,7 +852,10 @@ void pack_blob(int ksb, int bpnet_dim, const float *const *w, const float *const
 
 extern "C" {
 
-size_t sgn_mlp_packed_bytes(void) { return sgn::mlp::TOTAL_BYTES; }
+size_t sgn_mlp_packed_bytes(int32_t bpnet_layers, int32_t bpnet_dim) {
+    const int ksb = sgn::mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    return ksb < 0 ? 0 : sgn::mlp::total_bytes_sg(ksb);
+}
 
 size_t sgn_mlp_section(int32_t which) {
     using namespace sgn::mlp;
@@ -861,29 +864,16 @@ size_t sgn_mlp_section(int32_t which) {
 
 size_t sgn_point_proj_bytes(int64_t n_points) { return (size_t)(n_points > 0 ? n_points : 0) * sgn::mlp::PROJ_BYTES_PER_POINT; }
 
-int sgn_point_project_subset(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
-                             const int64_t *d_count, void *d_proj, sgn_stream_t stream) {
-    using namespace sgn;
-    using namespace sgn::mlp;
-    SGN_REQUIRE(pt && d_packed && d_proj && d_idx && d_count, "null argument");
-    SGN_REQUIRE(pt->n_points >= 0 && (pt->n_points == 0 || pt->embedding), "embedding required");
-    if (pt->n_points == 0) return 0;
-    ProjArgs a{pt->embedding, pt->n_points, d_packed, (_Float16 *)d_proj, d_idx, d_count};
-    // persistent grid over the device count (a frame names ~19 % of the points)
-    const int64_t waves = (pt->n_points + 31) / 32;
-    const int64_t wg = (waves + PROJ_TPB / 64 - 1) / (PROJ_TPB / 64);
-    hipLaunchKernelGGL(k_point_proj, dim3((unsigned)(wg < 256 ? wg : 256)), dim3(PROJ_TPB), 0, as_stream(stream), a);
-    SGN_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int sgn_point_project(const sgn_point_tables *pt, const void *d_packed, void *d_proj, sgn_stream_t stream) {
+int sgn_point_project(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx, const int64_t *d_count,
+                      void *d_proj, sgn_stream_t stream) {
     using namespace sgn;
     using namespace sgn::mlp;
     SGN_REQUIRE(pt && d_packed && d_proj, "null argument");
+    SGN_REQUIRE((d_idx == nullptr) == (d_count == nullptr), "d_idx and d_count go together (both null: every point)");
     SGN_REQUIRE(pt->n_points >= 0 && (pt->n_points == 0 || pt->embedding), "embedding required");
     if (pt->n_points == 0) return 0;
-    ProjArgs a{pt->embedding, pt->n_points, d_packed, (_Float16 *)d_proj};
+    ProjArgs a{pt->embedding, pt->n_points, d_packed, (_Float16 *)d_proj, d_idx, d_count};
+    // persistent grid: with a list it runs over the device count (a frame names ~19 % of the points)
     const int64_t waves = (pt->n_points + 31) / 32;
     const int64_t wg = (waves + PROJ_TPB / 64 - 1) / (PROJ_TPB / 64);
     hipLaunchKernelGGL(k_point_proj, dim3((unsigned)(wg < 256 ? wg : 256)), dim3(PROJ_TPB), 0, as_stream(stream), a);
@@ -891,24 +881,13 @@ int sgn_point_project(const sgn_point_tables *pt, const void *d_packed, void *d_
     return 0;
 }
 
-static int mlp_variant_ksb(int32_t bpnet_layers, int32_t bpnet_dim) {
-    if (bpnet_layers == 0) return 0;
-    if (bpnet_layers == 1 && (bpnet_dim == 0 || bpnet_dim == sgn::mlp::BP_DIM)) return sgn::mlp::ks_bp(bpnet_dim);
-    return -1;
-}
-
-size_t sgn_mlp_packed_bytes_sg(int32_t bpnet_layers, int32_t bpnet_dim) {
-    const int ksb = mlp_variant_ksb(bpnet_layers, bpnet_dim);
-    return ksb < 0 ? 0 : sgn::mlp::total_bytes_sg(ksb);
-}
-
-int sgn_mlp_pack_sg(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
-                    void *d_packed, sgn_stream_t stream) {
+int sgn_mlp_pack(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
+                 void *d_packed, sgn_stream_t stream) {
     using namespace sgn;
     using namespace sgn::mlp;
+    const int ksb = variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
     SGN_REQUIRE(w && b && d_packed, "null argument");
-    const int ksb = mlp_variant_ksb(bpnet_layers, bpnet_dim);
-    SGN_REQUIRE(ksb >= 0, "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
     if (ksb > 0) SGN_REQUIRE(w[9] && b[9], "block2_bpnet.0 weights missing");
     std::vector<uint8_t> blob(total_bytes_sg(ksb), 0);
     pack_blob(ksb, bpnet_dim, w, b, (_Float16 *)blob.data(), (float *)(blob.data() + OFF_F32),
@@ -919,38 +898,26 @@ int sgn_mlp_pack_sg(int32_t bpnet_layers, int32_t bpnet_dim, const float *const 
     return 0;
 }
 
-int sgn_mlp_pack(const float *const *w, const float *const *b, void *d_packed, sgn_stream_t stream) {
-    return sgn_mlp_pack_sg(0, 0, w, b, d_packed, stream);
-}
-
-/* Index maps of the base forward blob over the flat parameter vector (LAYERS order, each
- * layer weight row-major then bias): out[i] = flat index + 1, 0 = zero padding.
- * which 0: fragment part (OFF_F32 / 2 fp16 elements), 1: fp32 section (N_F32),
- * 2: split block1.0 sections [OFF_W0B, TOTAL_BYTES) as fp16 elements. */
-int sgn_mlp_pack_index(int32_t which, int32_t *out, int64_t n) {
+/* Index maps of the blob over the flat parameter vector (mlp_layout.h: IndexWeights):
+ * out[i] = flat index + 1, 0 = zero padding.  which 0: fragment part (OFF_F32 / 2 fp16 elements),
+ * 1: fp32 section (N_F32), 2: split block1.0 sections [OFF_W0B, TOTAL_BYTES) as fp16 elements;
+ * SG only: 3: block2_bpnet fragments [OFF_WB, off_bb) as fp16 elements, 4: its bias (HID fp32,
+ * accumulator order). */
+int sgn_mlp_pack_index(int32_t bpnet_layers, int32_t bpnet_dim, int32_t which, int32_t *out, int64_t n) {
     using namespace sgn;
     using namespace sgn::mlp;
+    const int ksb = variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
     const int64_t want = which == 0 ? (int64_t)(OFF_F32 / 2) : which == 1 ? (int64_t)N_F32
-                       : which == 2 ? (int64_t)((TOTAL_BYTES - OFF_W0B) / 2) : -1;
+                       : which == 2 ? (int64_t)((TOTAL_BYTES - OFF_W0B) / 2)
+                       : which == 3 && ksb > 0 ? (int64_t)((off_bb(ksb) - OFF_WB) / 2)
+                       : which == 4 && ksb > 0 ? (int64_t)HID : -1;
     SGN_REQUIRE(out && n == want, "sgn_mlp_pack_index: bad map id or size");
-    static const int shape[9][2] = {{256, 284}, {256, 256}, {256, 263}, {256, 256}, {1, 256},
-                                    {128, 280}, {128, 128}, {128, 128}, {3, 128}};
-    std::vector<std::vector<float>> wi(9), bi(9);
-    std::vector<const float *> wp(9), bp(9);
-    int64_t off = 0;
-    for (int L = 0; L < 9; ++L) {
-        wi[L].resize((size_t)shape[L][0] * shape[L][1]);
-        for (size_t i = 0; i < wi[L].size(); ++i) wi[L][i] = (float)(off + (int64_t)i + 1);
-        off += (int64_t)wi[L].size();
-        bi[L].resize(shape[L][0]);
-        for (size_t i = 0; i < bi[L].size(); ++i) bi[L][i] = (float)(off + (int64_t)i + 1);
-        off += (int64_t)bi[L].size();
-        wp[L] = wi[L].data();
-        bp[L] = bi[L].data();
-    }
-    std::vector<float> e16(TOTAL_BYTES / 2, 0.f), F(N_F32, 0.f);
-    pack_blob<float>(0, 0, wp.data(), bp.data(), e16.data(), F.data(), nullptr);
-    const float *src = which == 0 ? e16.data() : which == 1 ? F.data() : e16.data() + OFF_W0B / 2;
+    const IndexWeights iw(ksb, bpnet_dim);
+    std::vector<float> e16(total_bytes_sg(ksb) / 2, 0.f), F(N_F32, 0.f), BB(HID, 0.f);
+    pack_blob<float>(ksb, bpnet_dim, iw.wp.data(), iw.bp.data(), e16.data(), F.data(), BB.data());
+    const float *src = which == 0 ? e16.data() : which == 1 ? F.data() : which == 2 ? e16.data() + OFF_W0B / 2
+                     : which == 3 ? e16.data() + OFF_WB / 2 : BB.data();
     for (int64_t i = 0; i < n; ++i) out[i] = (int32_t)src[i];
     return 0;
 }
@@ -966,15 +933,15 @@ size_t sgn_aggregate_workspace_bytes(int64_t S) {
     return (size_t)S * sgn::mlp::HID * sizeof(_Float16);
 }
 
-int sgn_aggregate_sg(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f16, const void *d_point_proj,
-                     const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
-                     const void *d_packed, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
-                     void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream) {
+int sgn_aggregate(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f16, const void *d_point_proj,
+                  const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
+                  const void *d_packed, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
+                  void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream) {
     using namespace sgn;
     using namespace sgn::mlp;
+    const int ksb = variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
     SGN_REQUIRE(pt && q && d_packed && d_out_feat && d_workspace, "null argument");
-    const int ksb = mlp_variant_ksb(bpnet_layers, bpnet_dim);
-    SGN_REQUIRE(ksb >= 0, "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
     SGN_REQUIRE(ksb <= KS_HID || d_bpnet_f16, "bpnet_dim > 0 needs the fp16 BPNet point embedding");
     SGN_REQUIRE(K >= 1 && K <= 8, "the MFMA aggregator takes K = 1 .. 8 neighbours per sample");
     hipStream_t st = as_stream(stream);
@@ -986,15 +953,11 @@ int sgn_aggregate_sg(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpne
     const bool full = ws_items >= S_capacity;
     const int64_t chunk = ws_items < F16_MAX_CHUNK ? ws_items : F16_MAX_CHUNK;
     const uint8_t *P = (const uint8_t *)d_packed;
-    AggArgs a;
-    a.xyz = pt->xyz; a.emb = pt->embedding; a.color = pt->color; a.dir = pt->dir; a.conf = pt->conf;
-    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
-    a.pers = pt->pers; a.samp_pers = pt->samp_pers;
     SGN_REQUIRE((pt->pers == nullptr) == (pt->samp_pers == nullptr), "pers and samp_pers go together");
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir, "camera (campos, camrotc2w, raydir) required");
-    a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
-    a.samp_locw = q->samp_locw;
-    a.K = K;
+    AggArgs a{};
+    fill_agg_args(a, pt, q, K);
+    a.pers = pt->pers; a.samp_pers = pt->samp_pers;
     a.blob = P;
     a.blob_bytes = total_bytes_sg(ksb);
     a.bpnet = (const _Float16 *)d_bpnet_f16;
@@ -1028,45 +991,15 @@ int sgn_aggregate_sg(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpne
     return 0;
 }
 
-int sgn_aggregate_train_fwd(const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
+int sgn_aggregate_train_fwd(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f16,
+                            const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
                             const void *d_packed, float *d_out_feat, void *d_fs, const sgn_agg_saved *saved,
-                            sgn_stream_t stream) {
+                            void *d_h2b, sgn_stream_t stream) {
     using namespace sgn;
     using namespace sgn::mlp;
-    SGN_REQUIRE(pt && q && d_packed && d_out_feat && d_fs && saved, "null argument");
-    SGN_REQUIRE(saved->x0 && saved->h1 && saved->h2 && saved->h3, "null saved-activation buffer");
-    SGN_REQUIRE(K >= 1 && K <= 8, "the MFMA aggregator takes K = 1 .. 8 neighbours per sample");
-    SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir && !pt->pers, "camera required, no precomputed pers");
-    SGN_REQUIRE(S_capacity >= 0 && S_capacity < (1 << 27), "S_capacity out of range");
-    if (S_capacity == 0) return 0;
-    AggArgs a{};
-    a.xyz = pt->xyz; a.emb = pt->embedding; a.color = pt->color; a.dir = pt->dir; a.conf = pt->conf;
-    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
-    a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
-    a.samp_locw = q->samp_locw;
-    a.K = K;
-    a.blob = d_packed; a.blob_bytes = TOTAL_BYTES;
-    a.feat = d_out_feat; a.fs = (_Float16 *)d_fs;
-    a.item0 = 0; a.n_items = (int32_t)S_capacity;
-    a.sx0 = (_Float16 *)saved->x0; a.sh1 = (_Float16 *)saved->h1; a.sh2 = (_Float16 *)saved->h2;
-    a.sh3 = (_Float16 *)saved->h3;
-    int64_t wg = (S_capacity + WG_SAMPLES - 1) / WG_SAMPLES;
-    hipLaunchKernelGGL((k_agg_rows<0, true>), dim3((unsigned)(wg < 256 ? wg : 256)), dim3(ROWS_TPB), 0, as_stream(stream), a);
-    SGN_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int sgn_aggregate_train_fwd_sg(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f16,
-                               const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
-                               const void *d_packed, float *d_out_feat, void *d_fs, const sgn_agg_saved *saved,
-                               void *d_h2b, sgn_stream_t stream) {
-    using namespace sgn;
-    using namespace sgn::mlp;
-    const int ksb = mlp_variant_ksb(bpnet_layers, bpnet_dim);
-    SGN_REQUIRE(ksb >= 0, "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
-    if (ksb == 0)
-        return sgn_aggregate_train_fwd(pt, q, S_capacity, K, d_packed, d_out_feat, d_fs, saved, stream);
-    SGN_REQUIRE(pt && q && d_packed && d_out_feat && d_fs && saved && d_h2b, "null argument");
+    const int ksb = variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
+    SGN_REQUIRE(pt && q && d_packed && d_out_feat && d_fs && saved && (ksb == 0 || d_h2b), "null argument");
     SGN_REQUIRE(saved->x0 && saved->h1 && saved->h2 && saved->h3, "null saved-activation buffer");
     SGN_REQUIRE(ksb <= KS_HID || (d_bpnet_f16 && ((uintptr_t)d_bpnet_f16 & 15) == 0),
                 "bpnet_dim > 0 needs the 16-byte aligned fp16 BPNet point embedding");
@@ -1075,54 +1008,21 @@ int sgn_aggregate_train_fwd_sg(int32_t bpnet_layers, int32_t bpnet_dim, const vo
     SGN_REQUIRE(S_capacity >= 0 && S_capacity < (1 << 27), "S_capacity out of range");
     if (S_capacity == 0) return 0;
     AggArgs a{};
-    a.xyz = pt->xyz; a.emb = pt->embedding; a.color = pt->color; a.dir = pt->dir; a.conf = pt->conf;
-    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
-    a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
-    a.samp_locw = q->samp_locw;
-    a.K = K;
+    fill_agg_args(a, pt, q, K);
     a.blob = d_packed; a.blob_bytes = total_bytes_sg(ksb);
-    a.bpnet = (const _Float16 *)d_bpnet_f16;
     a.feat = d_out_feat; a.fs = (_Float16 *)d_fs;
     a.item0 = 0; a.n_items = (int32_t)S_capacity;
     a.sx0 = (_Float16 *)saved->x0; a.sh1 = (_Float16 *)saved->h1; a.sh2 = (_Float16 *)saved->h2;
-    a.sh3 = (_Float16 *)saved->h3; a.sh2b = (_Float16 *)d_h2b;
+    a.sh3 = (_Float16 *)saved->h3;
+    if (ksb > 0) {
+        a.bpnet = (const _Float16 *)d_bpnet_f16;
+        a.sh2b = (_Float16 *)d_h2b;
+    }
     const int64_t wg = (S_capacity + WG_SAMPLES - 1) / WG_SAMPLES;
-    auto kern = ksb == KS_HID ? k_agg_rows<KS_HID, true> : k_agg_rows<ks_bp(BP_DIM), true>;
+    auto kern = k_agg_rows<0, true>;
+    if (ksb > 0) kern = ksb == KS_HID ? k_agg_rows<KS_HID, true> : k_agg_rows<ks_bp(BP_DIM), true>;
     hipLaunchKernelGGL(kern, dim3((unsigned)(wg < 256 ? wg : 256)), dim3(ROWS_TPB), 0, as_stream(stream), a);
     SGN_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-/* Index maps of the SG blob's block2_bpnet sections over the flat parameter vector (the 9 base
- * layers, then block2_bpnet.0 weight [256][256 + bpnet_dim] and bias): which 3: fragments
- * [OFF_WB, off_bb) as fp16 elements, 4: the bias (HID fp32, accumulator order). */
-int sgn_mlp_pack_index_sg(int32_t bpnet_layers, int32_t bpnet_dim, int32_t which, int32_t *out, int64_t n) {
-    using namespace sgn;
-    using namespace sgn::mlp;
-    const int ksb = mlp_variant_ksb(bpnet_layers, bpnet_dim);
-    SGN_REQUIRE(ksb > 0, "sgn_mlp_pack_index_sg: block2_bpnet variant required");
-    const int64_t want = which == 3 ? (int64_t)((off_bb(ksb) - OFF_WB) / 2) : which == 4 ? (int64_t)HID : -1;
-    SGN_REQUIRE(out && n == want, "sgn_mlp_pack_index_sg: bad map id or size");
-    static const int shape[9][2] = {{256, 284}, {256, 256}, {256, 263}, {256, 256}, {1, 256},
-                                    {128, 280}, {128, 128}, {128, 128}, {3, 128}};
-    std::vector<std::vector<float>> wi(10), bi(10);
-    std::vector<const float *> wp(10), bp(10);
-    int64_t off = 0;
-    for (int L = 0; L < 10; ++L) {
-        const int o = L < 9 ? shape[L][0] : 256, i = L < 9 ? shape[L][1] : 256 + bpnet_dim;
-        wi[L].resize((size_t)o * i);
-        for (size_t j = 0; j < wi[L].size(); ++j) wi[L][j] = (float)(off + (int64_t)j + 1);
-        off += (int64_t)wi[L].size();
-        bi[L].resize(o);
-        for (size_t j = 0; j < bi[L].size(); ++j) bi[L][j] = (float)(off + (int64_t)j + 1);
-        off += (int64_t)bi[L].size();
-        wp[L] = wi[L].data();
-        bp[L] = bi[L].data();
-    }
-    std::vector<float> e16(total_bytes_sg(ksb) / 2, 0.f), F(N_F32, 0.f), BB(HID, 0.f);
-    pack_blob<float>(ksb, bpnet_dim, wp.data(), bp.data(), e16.data(), F.data(), BB.data());
-    const float *src = which == 3 ? e16.data() + OFF_WB / 2 : BB.data();
-    for (int64_t j = 0; j < n; ++j) out[j] = (int32_t)src[j];
     return 0;
 }
 
@@ -1139,13 +1039,6 @@ int sgn_bpnet_pack(const float *d_embedding, int64_t n_points, int32_t bpnet_dim
                        d_embedding, (_Float16 *)d_out_f16, n);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
-}
-
-int sgn_aggregate(const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
-                  const void *d_packed, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
-                  void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream) {
-    return sgn_aggregate_sg(0, 0, nullptr, nullptr, pt, q, S_capacity, K, d_packed, d_out_feat, d_out_blend, d_out_wnorm,
-                            d_workspace, workspace_bytes, stages, stream);
 }
 
 }  // extern "C"

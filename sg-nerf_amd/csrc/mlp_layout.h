@@ -16,6 +16,9 @@
 // the permutation is folded into the packed A columns so nothing moves at run time.
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
 
 namespace sgn {
 namespace mlp {
@@ -73,6 +76,52 @@ constexpr size_t OFF_WB = TOTAL_BYTES;                // block2_bpnet.0 fragment
 __host__ __device__ constexpr size_t off_bb(int ksb) { return OFF_WB + (size_t)T_HID * ksb * FRAG; }  // bias, acc order
 __host__ __device__ constexpr size_t total_bytes_sg(int ksb) { return ksb ? off_bb(ksb) + HID * 4 : TOTAL_BYTES; }
 constexpr size_t F_BB = N_F32;                        // bias slot after the base fp32 section (LDS copy)
+
+// The supported variants, as every entry point takes them: bpnet_layers 0 (the base network, any
+// bpnet_dim), or 1 with bpnet_dim 0 or 96.  Returns block2_bpnet.0's k-steps (0 = base), -1 for
+// anything else.
+constexpr int variant_ksb(int bpnet_layers, int bpnet_dim) {
+    return bpnet_layers == 0 ? 0 : bpnet_layers == 1 && (bpnet_dim == 0 || bpnet_dim == BP_DIM) ? ks_bp(bpnet_dim) : -1;
+}
+#define SGN_REQUIRE_VARIANT(ksb) \
+    SGN_REQUIRE((ksb) >= 0, "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96")
+
+// nn.Linear shapes [out][in] in the w[] / b[] order of every packer: block1.0, block1.2, block3.0,
+// block3.2, alpha_branch.0, color_branch.0, .2, .4, .6; layer 9 (SG) = block2_bpnet.0.  The flat
+// parameter vector holds them in this order, each weight row-major then its bias.
+constexpr int N_BASE_LAYERS = 9;
+constexpr int LAYER_SHAPE[N_BASE_LAYERS][2] = {{256, 284}, {256, 256}, {256, 263}, {256, 256}, {1, 256},
+                                               {128, 280}, {128, 128}, {128, 128}, {3, 128}};
+constexpr int layer_out(int L) { return L < N_BASE_LAYERS ? LAYER_SHAPE[L][0] : HID; }
+constexpr int layer_in(int L, int bpnet_dim) { return L < N_BASE_LAYERS ? LAYER_SHAPE[L][1] : HID + bpnet_dim; }
+constexpr size_t layer_weights(int L, int bpnet_dim) { return (size_t)layer_out(L) * layer_in(L, bpnet_dim); }
+// flat offset of layer L's weight (L = 9: the length of the base vector)
+constexpr int64_t flat_offset(int L) {
+    int64_t off = 0;
+    for (int l = 0; l < L; ++l) off += (int64_t)layer_weights(l, 0) + layer_out(l);
+    return off;
+}
+static_assert(flat_offset(N_BASE_LAYERS) == 341764, "the base flat vector (weights.N_PARAMS)");
+
+// Stand-in weights and biases whose values are their own flat index + 1: packing them with T = float
+// instead of fp16 turns a packer into its index map (0 = padding).  9 layers, 10 with ksb > 0.
+struct IndexWeights {
+    std::vector<std::vector<float>> w, b;
+    std::vector<const float *> wp, bp;
+    IndexWeights(int ksb, int bpnet_dim) {
+        const int nl = N_BASE_LAYERS + (ksb > 0);
+        w.resize(nl); b.resize(nl); wp.resize(nl); bp.resize(nl);
+        int64_t off = 0;
+        for (int L = 0; L < nl; ++L) {
+            w[L].resize(layer_weights(L, bpnet_dim));
+            for (float &v : w[L]) v = (float)++off;
+            b[L].resize(layer_out(L));
+            for (float &v : b[L]) v = (float)++off;
+            wp[L] = w[L].data();
+            bp[L] = b[L].data();
+        }
+    }
+};
 
 // unit of the 32-wide tile held by accumulator register r of lane-half h
 __host__ __device__ constexpr int acc_unit(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }

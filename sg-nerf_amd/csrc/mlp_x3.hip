@@ -1535,18 +1535,10 @@ int layer_shift(const float *W, size_t n) {
 }
 // ksb > 0: w[9] / b[9] = block2_bpnet.0 ([256][256 + bpnet_dim], [256])
 void pack_blob_x3(int ksb, int bpnet_dim, const float *const *w, const float *const *b, uint8_t *blob) {
-    static const int shape[9][2] = {{256, 284}, {256, 256}, {256, 263}, {256, 256}, {1, 256},
-                                    {128, 280}, {128, 128}, {128, 128}, {3, 128}};
     int s[9] = {};
-    for (int L : {0, 1, 2, 3, 5, 6, 7}) s[L] = layer_shift(w[L], (size_t)shape[L][0] * shape[L][1]);
-    const int sb = ksb > 0 ? layer_shift(w[9], (size_t)256 * (256 + bpnet_dim)) : 0;
+    for (int L : {0, 1, 2, 3, 5, 6, 7}) s[L] = layer_shift(w[L], layer_weights(L, 0));
+    const int sb = ksb > 0 ? layer_shift(w[9], layer_weights(9, bpnet_dim)) : 0;
     pack_blob16(ksb, bpnet_dim, w, b, s, sb, blob);
-}
-
-int variant_ksb(int32_t bpnet_layers, int32_t bpnet_dim) {
-    if (bpnet_layers == 0) return 0;
-    if (bpnet_layers == 1 && (bpnet_dim == 0 || bpnet_dim == BP_DIM)) return ks_bp(bpnet_dim);
-    return -1;
 }
 
 }  // namespace x3
@@ -1555,7 +1547,7 @@ int variant_ksb(int32_t bpnet_layers, int32_t bpnet_dim) {
 extern "C" {
 
 size_t sgn_mlp_packed_bytes_f32(int32_t bpnet_layers, int32_t bpnet_dim) {
-    const int ksb = sgn::x3::variant_ksb(bpnet_layers, bpnet_dim);
+    const int ksb = sgn::mlp::variant_ksb(bpnet_layers, bpnet_dim);
     return ksb < 0 ? 0 : sgn::x3::blob_bytes_sg(ksb);
 }
 
@@ -1563,8 +1555,8 @@ int sgn_mlp_pack_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *const
                      void *d_packed, sgn_stream_t stream) {
     using namespace sgn;
     SGN_REQUIRE(w && b && d_packed, "null argument");
-    const int ksb = x3::variant_ksb(bpnet_layers, bpnet_dim);
-    SGN_REQUIRE(ksb >= 0, "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
+    const int ksb = mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
     for (int L = 0; L < (ksb ? 10 : 9); ++L) SGN_REQUIRE(w[L] && b[L], "null layer pointer");
     std::vector<uint8_t> blob(x3::blob_bytes_sg(ksb), 0);
     x3::pack_blob_x3(ksb, bpnet_dim, w, b, blob.data());
@@ -1578,18 +1570,19 @@ int sgn_mlp_pack_f32_host(int32_t bpnet_layers, int32_t bpnet_dim, const float *
                           void *h_packed) {
     using namespace sgn;
     SGN_REQUIRE(w && b && h_packed, "null argument");
-    const int ksb = x3::variant_ksb(bpnet_layers, bpnet_dim);
-    SGN_REQUIRE(ksb >= 0, "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
+    const int ksb = mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
     for (int L = 0; L < (ksb ? 10 : 9); ++L) SGN_REQUIRE(w[L] && b[L], "null layer pointer");
     std::fill_n((uint8_t *)h_packed, x3::blob_bytes_sg(ksb), (uint8_t)0);
     x3::pack_blob_x3(ksb, bpnet_dim, w, b, (uint8_t *)h_packed);
     return 0;
 }
 
-int sgn_point_project_f32_subset(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
-                                 const int64_t *d_count, void *d_proj, sgn_stream_t stream) {
+int sgn_point_project_f32(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
+                          const int64_t *d_count, void *d_proj, sgn_stream_t stream) {
     using namespace sgn;
-    SGN_REQUIRE(pt && d_packed && d_proj && d_idx && d_count, "null argument");
+    SGN_REQUIRE(pt && d_packed && d_proj, "null argument");
+    SGN_REQUIRE((d_idx == nullptr) == (d_count == nullptr), "d_idx and d_count go together (both null: every point)");
     SGN_REQUIRE(pt->n_points >= 0 && (pt->n_points == 0 || pt->embedding), "embedding required");
     SGN_REQUIRE(((uintptr_t)d_proj & 15) == 0 && ((uintptr_t)pt->embedding & 15) == 0, "16-byte alignment required");
     if (pt->n_points == 0) return 0;
@@ -1597,7 +1590,7 @@ int sgn_point_project_f32_subset(const sgn_point_tables *pt, const void *d_packe
     float *rec = (float *)((char *)d_proj + (size_t)pt->n_points * x3::PROJ_BYTES_PER_POINT);
     x3::Proj16Args a{pt->embedding, pt->n_points, d_packed, (float *)d_proj, pt->xyz, pt->color, pt->dir,
                      pt->conf, rec, d_idx, d_count};
-    // persistent grid over the device count (a training step touches ~50 k of 1.2 M points)
+    // persistent grid: with a list it runs over the device count (a training step touches ~50 k of 1.2 M points)
     const int64_t tiles = (pt->n_points + 16 * x3::NW16 - 1) / (16 * x3::NW16);
     hipLaunchKernelGGL(x3::k_point_proj16, dim3((unsigned)(tiles < 256 ? tiles : 256)), dim3(x3::TPB16), 0,
                        as_stream(stream), a);
@@ -1610,26 +1603,9 @@ size_t sgn_point_proj_bytes_f32(int64_t n_points) {
     return (size_t)(n_points > 0 ? n_points : 0) * (sgn::x3::PROJ_BYTES_PER_POINT + sgn::x3::REC16_FLOATS * 4);
 }
 
-int sgn_point_project_f32(const sgn_point_tables *pt, const void *d_packed, void *d_proj, sgn_stream_t stream) {
-    using namespace sgn;
-    SGN_REQUIRE(pt && d_packed && d_proj, "null argument");
-    SGN_REQUIRE(pt->n_points >= 0 && (pt->n_points == 0 || pt->embedding), "embedding required");
-    SGN_REQUIRE(((uintptr_t)d_proj & 15) == 0 && ((uintptr_t)pt->embedding & 15) == 0, "16-byte alignment required");
-    if (pt->n_points == 0) return 0;
-    SGN_REQUIRE(pt->xyz && pt->color && pt->dir && pt->conf, "point tables (xyz, color, dir, conf) required");
-    float *rec = (float *)((char *)d_proj + (size_t)pt->n_points * x3::PROJ_BYTES_PER_POINT);
-    x3::Proj16Args a{pt->embedding, pt->n_points, d_packed, (float *)d_proj, pt->xyz, pt->color, pt->dir,
-                     pt->conf, rec, nullptr, nullptr};
-    const int64_t tiles = (pt->n_points + 16 * x3::NW16 - 1) / (16 * x3::NW16);
-    hipLaunchKernelGGL(x3::k_point_proj16, dim3((unsigned)(tiles < 256 ? tiles : 256)), dim3(x3::TPB16), 0,
-                       as_stream(stream), a);
-    SGN_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 // Workspace: blended features of every work item (fp32, 1 KiB each), so the two stages may be
 // called separately, then k_pair_slots' row table (32 B) and slot entries (16 B) per item, then a
-// 2-KiB tail: [0] the slot count, [1] the fp16-range flag (k_color16; sgn_aggregate_check_f32).
+// 2-KiB tail: [0] the slot count, [1] the fp16-range flag (k_color16; sgn_aggregate_flag_offset_f32).
 // A smaller workspace is accepted with stages = 3 (both stages per chunk).
 constexpr int64_t WS_PER_ITEM = sgn::mlp::HID * 4 + 32 + 16, WS_TAIL = 2048;
 size_t sgn_aggregate_workspace_bytes_f32(int64_t S) {
@@ -1656,8 +1632,8 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
     using namespace sgn::mlp;
     SGN_REQUIRE(pt && q && d_packed && d_out_feat && d_workspace && d_point_proj, "null argument");
     SGN_REQUIRE(stages >= 1 && stages <= 3, "stages must be 1 (rows), 2 (colour) or 3 (both)");
-    const int ksb = x3::variant_ksb(bpnet_layers, bpnet_dim);
-    SGN_REQUIRE(ksb >= 0, "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
+    const int ksb = mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
     SGN_REQUIRE(bpnet_dim == 0 || (d_bpnet && ((uintptr_t)d_bpnet & 15) == 0),
                 "bpnet_dim > 0 needs the 16-byte aligned fp32 BPNet point embedding");
     SGN_REQUIRE(K >= 1 && K <= 8, "the fp32 MFMA aggregator takes K = 1 .. 8 neighbours per sample");
@@ -1677,12 +1653,8 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
     const int64_t lim = ws_items < (1 << 27) ? ws_items : (1 << 27);
     const int64_t chunk = lim < S_capacity ? lim : (S_capacity > 32 ? S_capacity : 32);
     AggArgs a{};
-    a.xyz = pt->xyz; a.emb = pt->embedding; a.color = pt->color; a.dir = pt->dir; a.conf = pt->conf;
-    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
+    fill_agg_args(a, pt, q, K);
     a.pers = pt->pers; a.samp_pers = pt->samp_pers;
-    a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
-    a.samp_locw = q->samp_locw;
-    a.K = K;
     a.blob = d_packed; a.blob_bytes = x3::blob_bytes_sg(ksb);
     a.bpnet32 = d_bpnet;
     a.proj = (const _Float16 *)d_point_proj;  // fp32 P table (k_rows16 reads it as float)
@@ -1756,26 +1728,15 @@ int sgn_aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bp
                          d_out_blend, d_out_wnorm, d_workspace, workspace_bytes, stages, stream);
 }
 
-int sgn_aggregate_train_fwd_f32(const void *d_point_proj, const sgn_point_tables *pt, const sgn_query_out *q,
-                                int64_t S_capacity, int32_t K, const void *d_packed, float *d_out_feat,
-                                float *d_z1, float *d_z2, float *d_z3, const int32_t *d_row_off, void *d_workspace,
+int sgn_aggregate_train_fwd_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
+                                const void *d_point_proj, const sgn_point_tables *pt, const sgn_query_out *q,
+                                int64_t S_capacity, int32_t K, const void *d_packed, float *d_out_feat, float *d_z1,
+                                float *d_z2, float *d_zb, float *d_z3, const int32_t *d_row_off, void *d_workspace,
                                 size_t workspace_bytes, sgn_stream_t stream) {
+    SGN_REQUIRE_VARIANT(sgn::mlp::variant_ksb(bpnet_layers, bpnet_dim));
+    if (bpnet_layers == 0) d_zb = nullptr;  // the base network has no block2_bpnet.0 to save
+    else SGN_REQUIRE(d_zb, "null block2_bpnet pre-activation buffer zb");
     SGN_REQUIRE(d_z1 && d_z2 && d_z3 && ((uintptr_t)d_z1 & 15) == 0 && ((uintptr_t)d_z2 & 15) == 0 &&
-                    ((uintptr_t)d_z3 & 15) == 0,
-                "16-byte aligned pre-activation buffers z1, z2, z3 required");
-    SGN_REQUIRE(pt && pt->pers == nullptr, "the training forward computes the pers coordinates itself");
-    float *const z[4] = {d_z1, d_z2, d_z3, nullptr};
-    return aggregate_f32(0, 0, nullptr, d_point_proj, pt, q, S_capacity, K, d_packed, d_out_feat, nullptr, nullptr,
-                         d_workspace, workspace_bytes, 1, stream, z, d_row_off);
-}
-
-int sgn_aggregate_train_fwd_f32_sg(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
-                                   const void *d_point_proj, const sgn_point_tables *pt, const sgn_query_out *q,
-                                   int64_t S_capacity, int32_t K, const void *d_packed, float *d_out_feat, float *d_z1,
-                                   float *d_z2, float *d_zb, float *d_z3, const int32_t *d_row_off, void *d_workspace,
-                                   size_t workspace_bytes, sgn_stream_t stream) {
-    SGN_REQUIRE(bpnet_layers == 1, "the SG training forward has one block2_bpnet layer");
-    SGN_REQUIRE(d_z1 && d_z2 && d_zb && d_z3 && ((uintptr_t)d_z1 & 15) == 0 && ((uintptr_t)d_z2 & 15) == 0 &&
                     ((uintptr_t)d_zb & 15) == 0 && ((uintptr_t)d_z3 & 15) == 0,
                 "16-byte aligned pre-activation buffers z1, z2, zb, z3 required");
     SGN_REQUIRE(pt && pt->pers == nullptr, "the training forward computes the pers coordinates itself");
@@ -1786,8 +1747,8 @@ int sgn_aggregate_train_fwd_f32_sg(int32_t bpnet_layers, int32_t bpnet_dim, cons
 
 int sgn_mlp_pack_index_f32(int32_t bpnet_layers, int32_t bpnet_dim, int32_t which, int32_t *out, int64_t n) {
     using namespace sgn;
-    const int ksb = x3::variant_ksb(bpnet_layers, bpnet_dim);
-    SGN_REQUIRE(ksb >= 0, "block2_bpnet: supported are 0 layers, or 1 layer with bpnet_dim 0 or 96");
+    const int ksb = mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
     SGN_REQUIRE(out && (which == 0 || which == 1), "which: 0 fragment section, 1 fp32 section");
     const size_t n16 = x3::OFF16_F32 / 2, n32 = x3::N_Y32;
     SGN_REQUIRE((size_t)n == (which == 0 ? n16 : n32), "index map length (sgn_mlp_layout_f32)");
@@ -1801,20 +1762,6 @@ int sgn_mlp_pack_index_f32(int32_t bpnet_layers, int32_t bpnet_dim, int32_t whic
 int64_t sgn_mlp_layout_f32(int32_t which) {
     // 0: bytes of the fragment section (= byte offset of the fp32 section), 1: fp32 entries after it
     return which == 0 ? (int64_t)sgn::x3::OFF16_F32 : which == 1 ? (int64_t)sgn::x3::N_Y32 : -1;
-}
-
-int sgn_aggregate_check_f32(const void *d_workspace, size_t workspace_bytes, sgn_stream_t stream) {
-    using namespace sgn;
-    SGN_REQUIRE(d_workspace && workspace_bytes >= (size_t)(32 * WS_PER_ITEM + WS_TAIL), "null or too small workspace");
-    const int32_t *flag = ws_tail(const_cast<void *>(d_workspace), workspace_bytes) + 1;
-    int32_t h = 0;
-    hipStream_t st = as_stream(stream);
-    SGN_CHECK_HIP(hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, st));
-    SGN_CHECK_HIP(hipStreamSynchronize(st));
-    SGN_REQUIRE(h == 0, "fp16 range exceeded: an aggregator activation or point feature reached |x| >= 65504, so "
-                        "the split-fp16 MFMA operands overflowed and the decoded features of the last "
-                        "sgn_aggregate_f32 call are not finite");
-    return 0;
 }
 
 int64_t sgn_aggregate_fs_offset_f32(size_t workspace_bytes, int64_t S_capacity) {

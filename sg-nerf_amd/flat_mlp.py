@@ -126,8 +126,8 @@ class _Packer:
     def __init__(self, device, variant=(0, 0)):
         L = _lib.lib()
         self.variant = variant
-        self.base = int(L.sgn_mlp_packed_bytes())
-        self.total = int(L.sgn_mlp_packed_bytes_sg(*variant)) if variant != (0, 0) else self.base
+        self.base = int(L.sgn_mlp_section(2))
+        self.total = int(L.sgn_mlp_packed_bytes(*variant))
         self.off_f32 = int(L.sgn_mlp_section(0))
         self.off_split = int(L.sgn_mlp_section(1))
         self.tbytes = int(L.sgn_train_tblob_bytes())
@@ -135,19 +135,16 @@ class _Packer:
         def imap(fn, name, *args, n):
             """The layout's index map (flat index + 1, 0 = zero) as flat indices (-1 = zero)."""
             a = (ctypes.c_int32 * n)()
-            _lib.check(fn(*args, a, n), name)
+            _lib.check(fn(*variant, *args, a, n), name)
             return (torch.frombuffer(bytearray(a), dtype=torch.int32) - 1).to(device)
         self.i16 = imap(L.sgn_mlp_pack_index, "sgn_mlp_pack_index", 0, n=self.off_f32 // 2)
         self.i32 = imap(L.sgn_mlp_pack_index, "sgn_mlp_pack_index", 1, n=N_F32)
         self.isp = imap(L.sgn_mlp_pack_index, "sgn_mlp_pack_index", 2, n=(self.base - self.off_split) // 2)
         if variant != (0, 0):
             self.off_bb = self.total - 4 * 256                   # block2_bpnet bias (fp32, acc order)
-            self.iwb = imap(L.sgn_mlp_pack_index_sg, "sgn_mlp_pack_index_sg", *variant, 3,
-                            n=(self.off_bb - self.base) // 2)
-            self.ibb = imap(L.sgn_mlp_pack_index_sg, "sgn_mlp_pack_index_sg", *variant, 4, n=256)
-            self.it = imap(L.sgn_train_pack_index_sg, "sgn_train_pack_index_sg", variant[1], n=self.tbytes // 2)
-        else:
-            self.it = imap(L.sgn_train_pack_index, "sgn_train_pack_index", n=self.tbytes // 2)
+            self.iwb = imap(L.sgn_mlp_pack_index, "sgn_mlp_pack_index", 3, n=(self.off_bb - self.base) // 2)
+            self.ibb = imap(L.sgn_mlp_pack_index, "sgn_mlp_pack_index", 4, n=256)
+        self.it = imap(L.sgn_train_pack_index, "sgn_train_pack_index", n=self.tbytes // 2)
         self.blob = torch.zeros(self.total, dtype=torch.uint8, device=device)
         self.tblob = torch.zeros(self.tbytes, dtype=torch.uint8, device=device)
         # (index map, destination bytes, fp16?) -- every section of both blobs in one gather launch

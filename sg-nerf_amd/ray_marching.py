@@ -367,7 +367,7 @@ class PointAggregator:
         if self.f32:
             # block1.0's per-point part over the gathered rows (each row is its own "point")
             proj = torch.empty(int(L.sgn_point_proj_bytes_f32(S * K)), dtype=torch.uint8, device=dev)
-            _lib.check(L.sgn_point_project_f32(ctypes.byref(pt), _lib.ptr(self.packed), _lib.ptr(proj), st),
+            _lib.check(L.sgn_point_project_f32(ctypes.byref(pt), _lib.ptr(self.packed), None, None, _lib.ptr(proj), st),
                        "sgn_point_project_f32")
             ws = torch.empty(int(L.sgn_aggregate_workspace_bytes_f32(S)), dtype=torch.uint8, device=dev)
             _lib.check(L.sgn_aggregate_f32(nl, dim, _lib.ptr(bp), _lib.ptr(proj), ctypes.byref(pt), ctypes.byref(qo), S, K,
@@ -385,9 +385,9 @@ class PointAggregator:
             wnorm = torch.zeros_like(wnorm).scatter_(1, order, wnorm)   # back to the caller's slot order
         else:
             ws = torch.empty(int(L.sgn_aggregate_workspace_bytes(S)), dtype=torch.uint8, device=dev)
-            _lib.check(L.sgn_aggregate_sg(nl, dim, _lib.ptr(bp), None, ctypes.byref(pt), ctypes.byref(qo), S, K,
-                                          _lib.ptr(self.packed), _lib.ptr(feat), None, _lib.ptr(wnorm), _lib.ptr(ws),
-                                          ws.numel(), 3, st), "sgn_aggregate_sg")
+            _lib.check(L.sgn_aggregate(nl, dim, _lib.ptr(bp), None, ctypes.byref(pt), ctypes.byref(qo), S, K,
+                                       _lib.ptr(self.packed), _lib.ptr(feat), None, _lib.ptr(wnorm), _lib.ptr(ws),
+                                       ws.numel(), 3, st), "sgn_aggregate")
         # point_aggregators.py:951-953 (forward value of the straight-through clamp)
         conf_coef = torch.clamp(sampled_conf.to(dev)[..., 0], 1e-4, 1.0)
         return feat.view(shp + (4,)), ray_valid.view(shp), wnorm.view(shp + (K,)), conf_coef

@@ -220,9 +220,9 @@ class HipRenderer:
             _, marks, plist, pcount = self._fp
             _lib.check(L.sgn_frame_points(_lib.ptr(q.pidx), _lib.ptr(q.counters), q.pidx.numel() // o.K, o.K, n,
                                           _lib.ptr(marks), _lib.ptr(plist), _lib.ptr(pcount), st), "sgn_frame_points")
-            project = L.sgn_point_project_f32_subset if self.f32 else L.sgn_point_project_subset
+            project = L.sgn_point_project_f32 if self.f32 else L.sgn_point_project   # different arithmetic
             _lib.check(project(ctypes.byref(pt), _lib.ptr(self.packed), _lib.ptr(plist), _lib.ptr(pcount),
-                               _lib.ptr(self._proj), st), "point projection (subset)")
+                               _lib.ptr(self._proj), st), "point projection (frame list)")
         for stage, name in ((1, "agg_rows"), (2, "agg_color")):
             mark(name)
             blend = _lib.ptr(self.blend) if want_blend else None
@@ -235,9 +235,9 @@ class HipRenderer:
                                                _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
                                                _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate_f32")
             else:
-                _lib.check(L.sgn_aggregate_sg(nl, dim, bp, _lib.ptr(self._proj), ctypes.byref(pt), ctypes.byref(qo), cap,
-                                              o.K, _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
-                                              _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate_sg")
+                _lib.check(L.sgn_aggregate(nl, dim, bp, _lib.ptr(self._proj), ctypes.byref(pt), ctypes.byref(qo), cap,
+                                           o.K, _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
+                                           _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate")
         mark("composite")
         cp = _lib.CompositeParams()
         cp.SR, cp.vsize_z, cp.raydist_mode_unit = o.SR, float(o.vsize[2]), o.raydist_mode_unit

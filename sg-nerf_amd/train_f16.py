@@ -218,14 +218,10 @@ class F16Step:
             tr.packer32.pack(tr.mlp.flat)   # the colour GEMMs' weight shifts
             self.feat.zero_()               # samples without neighbours keep zero features
         saved = _lib.AggSaved(self.x0.data_ptr(), self.h1.data_ptr(), self.h2.data_ptr(), self.h3.data_ptr())
-        if n > 0 and tr.sg:
-            _lib.check(L.sgn_aggregate_train_fwd_sg(*tr.variant, _lib.ptr(tr.bpnet16), ctypes.byref(pt),
-                                                    ctypes.byref(qo), n, o.K, _lib.ptr(blob), _lib.ptr(self.feat),
-                                                    _lib.ptr(self.fs), ctypes.byref(saved), _lib.ptr(self.h2b), st),
-                       "sgn_aggregate_train_fwd_sg")
-        elif n > 0:
-            _lib.check(L.sgn_aggregate_train_fwd(ctypes.byref(pt), ctypes.byref(qo), n, o.K, _lib.ptr(blob),
-                                                 _lib.ptr(self.feat), _lib.ptr(self.fs), ctypes.byref(saved), st),
+        if n > 0:   # h2b / db (block2_bpnet's input and delta) exist for SG trainers only
+            _lib.check(L.sgn_aggregate_train_fwd(*tr.variant, _lib.ptr(tr.bpnet16), ctypes.byref(pt), ctypes.byref(qo),
+                                                 n, o.K, _lib.ptr(blob), _lib.ptr(self.feat), _lib.ptr(self.fs),
+                                                 ctypes.byref(saved), _lib.ptr(self.h2b), st),
                        "sgn_aggregate_train_fwd")
         # ---- colour MLP + composite + losses ------------------------------------------------
         if graph:
@@ -253,17 +249,11 @@ class F16Step:
             P = tr.points
             grads = _lib.PointGrads(P.points_embeding.grad.data_ptr(), P.points_color.grad.data_ptr(),
                                     P.points_dir.grad.data_ptr(), P.points_conf.grad.data_ptr())
-            if tr.sg:
-                _lib.check(L.sgn_aggregate_backward_sg(*tr.variant, ctypes.byref(pt), ctypes.byref(qo), n, o.K,
-                                                       _lib.ptr(blob), _lib.ptr(tblob), ctypes.byref(saved),
-                                                       _lib.ptr(self.h2b), _lib.ptr(dfs), _lib.ptr(dal),
-                                                       _lib.ptr(scale), ctypes.byref(deltas), _lib.ptr(self.db),
-                                                       ctypes.byref(grads), st), "sgn_aggregate_backward_sg")
-            else:
-                _lib.check(L.sgn_aggregate_backward(ctypes.byref(pt), ctypes.byref(qo), n, o.K, _lib.ptr(blob),
-                                                    _lib.ptr(tblob), ctypes.byref(saved), _lib.ptr(dfs), _lib.ptr(dal),
-                                                    _lib.ptr(scale), ctypes.byref(deltas), ctypes.byref(grads), st),
-                           "sgn_aggregate_backward")
+            _lib.check(L.sgn_aggregate_backward(*tr.variant, ctypes.byref(pt), ctypes.byref(qo), n, o.K,
+                                                _lib.ptr(blob), _lib.ptr(tblob), ctypes.byref(saved),
+                                                _lib.ptr(self.h2b), _lib.ptr(dfs), _lib.ptr(dal), _lib.ptr(scale),
+                                                ctypes.byref(deltas), _lib.ptr(self.db), ctypes.byref(grads), st),
+                       "sgn_aggregate_backward")
             self._weight_grads(n * 8, scale, q)
         parts["total"] = total.detach()
         return parts, full.detach(), ray_mask

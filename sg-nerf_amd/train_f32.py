@@ -9,7 +9,7 @@ as one captured graph:
 
   sgn_train_lists            deterministic work list + compact row offsets (prefix sums)
   sgn_aggregate_train_fwd_f32  k_pair_slots + k_rows16 (save mode): alpha_s, f_s, z1 / z2 / z3 rows
-                             (SG: _sg, + block2_bpnet.0's zb)
+                             (SG: + block2_bpnet.0's zb)
   sgn_train_row_inputs       x0 = [emb | PE(emb) | PE(dists) | 1], extra channels, blend weights,
                              PE(viewdir); SG: sgn_train_row_gather, the rows' BPNet embedding
   colour forward             3 x sgn_x3_gemm (x W^T + b, LeakyReLU) + sgn_train_colour_head (rgb)
@@ -263,6 +263,7 @@ class F32Step:
         self.lists_ws = torch.empty(int(L.sgn_train_lists_workspace_bytes(cap)), dtype=torch.uint8, device=dev)
         self.feat = torch.zeros(cap, 4, **f32)
         self.z = [torch.empty(rows, 256, **f32) for _ in range(4)]     # z1, z2, z3, z4 -> delta4
+        self.zb = self.db = self.bprow = None
         if self.sg:   # block2_bpnet.0's pre-activation and delta, the rows' BPNet embedding
             self.zb = torch.empty(rows, 256, **f32)
             self.db = torch.empty(rows, 256, **f32)
@@ -380,15 +381,10 @@ class F32Step:
         self.amax.zero_()
         ck(L.sgn_train_lists(p(self.q.counters), p(self.q.samp_nnb), cap, p(self.q.work), p(self.row_off), p(self.feat),
                              p(self.counts), p(self.lists_ws), st), "sgn_train_lists")
-        if self.sg:
-            ck(L.sgn_aggregate_train_fwd_f32_sg(1, self.D, p(tr.bpnet32) if self.D else None, p(proj), ctypes.byref(pt),
-                                                ctypes.byref(qo), cap, K, p(blob), p(self.feat), p(self.z[0]),
-                                                p(self.z[1]), p(self.zb), p(self.z[2]), p(self.row_off), p(self.ws32),
-                                                self.ws32.numel(), st), "sgn_aggregate_train_fwd_f32_sg")
-        else:
-            ck(L.sgn_aggregate_train_fwd_f32(p(proj), ctypes.byref(pt), ctypes.byref(qo), cap, K, p(blob), p(self.feat),
-                                             p(self.z[0]), p(self.z[1]), p(self.z[2]), p(self.row_off), p(self.ws32),
-                                             self.ws32.numel(), st), "sgn_aggregate_train_fwd_f32")
+        ck(L.sgn_aggregate_train_fwd_f32(*tr.variant, p(tr.bpnet32), p(proj), ctypes.byref(pt), ctypes.byref(qo), cap, K,
+                                         p(blob), p(self.feat), p(self.z[0]), p(self.z[1]), p(self.zb), p(self.z[2]),
+                                         p(self.row_off), p(self.ws32), self.ws32.numel(), st),
+           "sgn_aggregate_train_fwd_f32")
         ck(L.sgn_train_row_inputs(ctypes.byref(pt), ctypes.byref(qo), K, p(self.row_off), p(self.counts), p(self.x0),
                                   p(self.ext), p(self.rw), p(self.vpe), st), "sgn_train_row_inputs")
         if self.D:
@@ -420,7 +416,7 @@ class F32Runner:
       begin   the fp32-faithful blob re-packed, the point Adam's launch (HipTrainer._adam_rows: on the
               query's table, whose distinct-row list is then the step's touched list; under DP on the
               rank's touched rows, which ride the point-row exchange)
-      run     sgn_point_project_f32_subset (block1.0's per-point part for the touched points only: ~50 k
+      run     sgn_point_project_f32 on a list (block1.0's per-point part for the touched points only: ~50 k
               of 1.2 M for a 4096-ray batch -- the rows read no other point, and the weights change
               every step), F32Step.run, the results out into one fresh allocation"""
 
@@ -482,9 +478,8 @@ class F32Runner:
         if self.proj is None or self.proj.numel() < nproj:
             self.proj = torch.empty(max(nproj, 16), dtype=torch.uint8, device=dev)
         idx32, cnt = self._rows
-        _lib.check(L.sgn_point_project_f32_subset(ctypes.byref(pt), _lib.ptr(self._blob), _lib.ptr(idx32),
-                                                  _lib.ptr(cnt), _lib.ptr(self.proj), _lib.stream_handle()),
-                   "sgn_point_project_f32_subset")
+        _lib.check(L.sgn_point_project_f32(ctypes.byref(pt), _lib.ptr(self._blob), _lib.ptr(idx32), _lib.ptr(cnt),
+                                           _lib.ptr(self.proj), _lib.stream_handle()), "sgn_point_project_f32")
         fl = tr.mlp.flat
         key = (R, q.work.data_ptr(), q.pidx.data_ptr(), fl.data_ptr(), fl.grad.data_ptr())
         if self.key != key:

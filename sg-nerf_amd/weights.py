@@ -99,7 +99,7 @@ def pack_mlp(state, device, precision="f16"):
     layers = layers_for(nl, dim)
     L = _lib.lib()
     nbytes = int(L.sgn_mlp_packed_bytes_f32(nl, dim) if precision == "f32" else
-                 L.sgn_mlp_packed_bytes_exact(nl, dim) if precision == "exact" else L.sgn_mlp_packed_bytes_sg(nl, dim))
+                 L.sgn_mlp_packed_bytes_exact(nl, dim) if precision == "exact" else L.sgn_mlp_packed_bytes(nl, dim))
     out = torch.empty(nbytes, dtype=torch.uint8, device=device)
     ws = [np.ascontiguousarray(torch.as_tensor(state[n + ".weight"]).detach().cpu().float().numpy()) for n, *_ in layers]
     bs = [np.ascontiguousarray(torch.as_tensor(state[n + ".bias"]).detach().cpu().float().numpy()) for n, *_ in layers]
@@ -116,5 +116,5 @@ def pack_mlp(state, device, precision="f16"):
         elif precision == "exact":   # plain fp32 W^T for the range fallback (sgn_aggregate_exact)
             _lib.check(L.sgn_mlp_pack_exact(nl, dim, wp, bp, _lib.ptr(out), _lib.stream_handle()), "sgn_mlp_pack_exact")
         else:
-            _lib.check(L.sgn_mlp_pack_sg(nl, dim, wp, bp, _lib.ptr(out), _lib.stream_handle()), "sgn_mlp_pack_sg")
+            _lib.check(L.sgn_mlp_pack(nl, dim, wp, bp, _lib.ptr(out), _lib.stream_handle()), "sgn_mlp_pack")
     return out

@@ -71,7 +71,7 @@ def test_integration_snippet_matches_binding():
 
 def test_sizing_functions():
     L = _lib.lib()
-    assert L.sgn_mlp_packed_bytes() > 2 * N_PARAMS  # fp16 fragments (+ padding) + fp32 params
+    assert L.sgn_mlp_packed_bytes(0, 0) > 2 * N_PARAMS  # fp16 fragments (+ padding) + fp32 params
     assert L.sgn_query_workspace_bytes(2000) >= L.sgn_query_workspace_bytes(1000) > 0
     assert L.sgn_aggregate_workspace_bytes(10_000) >= 10_000 * 256 * 2
 
@@ -83,7 +83,8 @@ def test_argument_errors_are_reported_without_gpu():
     pt, qo = _lib.PointTables(), _lib.QueryOut()
     for f in ("xyz", "embedding", "color", "dir", "conf", "campos", "camrotc2w", "raydir"):
         setattr(pt, f, 16)
-    rc = L.sgn_aggregate(ctypes.byref(pt), ctypes.byref(qo), 64, 9, fake, fake, None, None, fake, 1 << 20, 3, None)
+    rc = L.sgn_aggregate(0, 0, None, None, ctypes.byref(pt), ctypes.byref(qo), 64, 9, fake, fake, None, None, fake,
+                         1 << 20, 3, None)
     assert rc != 0 and b"K = 1 .. 8" in L.sgn_last_error()
     with pytest.raises(_lib.SgnError, match="K = 1 .. 8"):
         _lib.check(rc, "sgn_aggregate")
@@ -109,7 +110,7 @@ def test_argument_errors_are_reported_without_gpu():
     rc = L.sgn_aggregate_f32(0, 0, None, fake, ctypes.byref(pt), ctypes.byref(qo), 64, 16, fake, fake, None, None,
                              fake, 1 << 20, 3, None)
     assert rc != 0 and b"K = 1 .. 8" in L.sgn_last_error()
-    rc = L.sgn_point_project_f32_subset(ctypes.byref(pt), fake, None, fake, fake, None)
+    rc = L.sgn_point_project_f32(ctypes.byref(pt), fake, None, fake, fake, None)
     assert rc != 0 and b"null" in L.sgn_last_error()
     # plain-fp32 range fallback: K, the SG variant, the workspace
     rc = L.sgn_aggregate_exact(0, 0, None, ctypes.byref(pt), ctypes.byref(qo), 64, 9, fake, fake, None, None, fake,
@@ -275,12 +276,12 @@ def test_sg_variant_options_and_weights():
 def test_sg_abi_sizes():
     from sgnerf_amd import _lib
     L = _lib.lib()
-    base = int(L.sgn_mlp_packed_bytes())
-    assert int(L.sgn_mlp_packed_bytes_sg(0, 0)) == base
-    assert int(L.sgn_mlp_packed_bytes_sg(1, 96)) == base + 8 * 22 * 1024 + 1024
-    assert int(L.sgn_mlp_packed_bytes_sg(1, 0)) == base + 8 * 16 * 1024 + 1024
-    assert int(L.sgn_mlp_packed_bytes_sg(2, 96)) == 0
-    assert int(L.sgn_mlp_packed_bytes_sg(1, 32)) == 0
+    base = int(L.sgn_mlp_section(2))
+    assert int(L.sgn_mlp_packed_bytes(0, 0)) == base
+    assert int(L.sgn_mlp_packed_bytes(1, 96)) == base + 8 * 22 * 1024 + 1024
+    assert int(L.sgn_mlp_packed_bytes(1, 0)) == base + 8 * 16 * 1024 + 1024
+    assert int(L.sgn_mlp_packed_bytes(2, 96)) == 0
+    assert int(L.sgn_mlp_packed_bytes(1, 32)) == 0
 
 
 def test_training_pack_index_maps():
@@ -288,10 +289,10 @@ def test_training_pack_index_maps():
     host packers do (flat LAYERS order)."""
     from sgnerf_amd.weights import N_PARAMS
     L = _lib.lib()
-    total = int(L.sgn_mlp_packed_bytes())
+    total = int(L.sgn_mlp_packed_bytes(0, 0))
     n16, n32 = int(L.sgn_mlp_section(0)) // 2, 2056
     a16, a32 = (ctypes.c_int32 * n16)(), (ctypes.c_int32 * n32)()
-    assert L.sgn_mlp_pack_index(0, a16, n16) == 0 and L.sgn_mlp_pack_index(1, a32, n32) == 0
+    assert L.sgn_mlp_pack_index(0, 0, 0, a16, n16) == 0 and L.sgn_mlp_pack_index(0, 0, 1, a32, n32) == 0
     m16, m32 = np.frombuffer(a16, np.int32), np.frombuffer(a32, np.int32)
     # block1/3 + colour hidden weights live in fragments: each exactly once
     used16 = np.bincount(m16[m16 > 0], minlength=N_PARAMS + 1)
@@ -303,13 +304,13 @@ def test_training_pack_index_maps():
     # split block1.0 sections: block1.0's weights once each (W0b: PE(dists) columns, W0a: the rest)
     nsp = (total - int(L.sgn_mlp_section(1))) // 2
     asp = (ctypes.c_int32 * nsp)()
-    assert L.sgn_mlp_pack_index(2, asp, nsp) == 0
+    assert L.sgn_mlp_pack_index(0, 0, 2, asp, nsp) == 0
     msp = np.frombuffer(asp, np.int32)
     usp = np.bincount(msp[msp > 0], minlength=N_PARAMS + 1)
     assert usp.max() == 1 and int((usp > 0).sum()) == 256 * 284 and int(usp[1:256 * 284 + 1].sum()) == 256 * 284
     nt = int(L.sgn_train_tblob_bytes()) // 2
     at = (ctypes.c_int32 * nt)()
-    assert L.sgn_train_pack_index(at, nt) == 0
+    assert L.sgn_train_pack_index(0, 0, at, nt) == 0
     mt = np.frombuffer(at, np.int32)
     ut = np.bincount(mt[mt > 0], minlength=N_PARAMS + 1)
     assert ut.max() == 1 and int((ut > 0).sum()) == 256 * (284 + 256 + 263 + 256)
@@ -320,3 +321,84 @@ def test_training_pack_index_maps():
     assert L.sgn_train_colmap(1, c1, 288) == 0
     v1 = np.frombuffer(c1, np.int32)
     assert sorted(v1[v1 >= 0].tolist()) == list(range(284))
+
+
+def _index_map(fn, *args, n):
+    a = (ctypes.c_int32 * n)()
+    assert fn(*args, a, n) == 0, _lib.lib().sgn_last_error()
+    return np.frombuffer(a, np.int32).copy()
+
+
+@pytest.mark.parametrize("dim", [0, 96])
+def test_sg_pack_index_maps(dim):
+    """The block2_bpnet sections of both blobs over the SG flat vector (the 9 base layers, then
+    block2_bpnet.0's weight [256][256 + dim] and bias): every element named exactly once."""
+    L = _lib.lib()
+    base, total = int(L.sgn_mlp_section(2)), int(L.sgn_mlp_packed_bytes(1, dim))
+    w0, nw = N_PARAMS, 256 * (256 + dim)          # flat span of block2_bpnet.0's weight, then its bias
+    m3 = _index_map(L.sgn_mlp_pack_index, 1, dim, 3, n=(total - 1024 - base) // 2)
+    assert sorted(m3[m3 > 0].tolist()) == list(range(w0 + 1, w0 + nw + 1)) and m3.min() >= 0
+    m4 = _index_map(L.sgn_mlp_pack_index, 1, dim, 4, n=256)
+    assert sorted(m4.tolist()) == list(range(w0 + nw + 1, w0 + nw + 257))
+    # transposed blob: the four row-layer weights once each + block2_bpnet.0's first 256 input columns
+    nt = int(L.sgn_train_tblob_bytes()) // 2
+    mt = _index_map(L.sgn_train_pack_index, 1, dim, n=nt)
+    want, off = [], 0
+    for _, o, i, _ in LAYERS[:4]:
+        want += range(off + 1, off + o * i + 1)
+        off += o * i + o
+    want += [w0 + 1 + r * (256 + dim) + c for r in range(256) for c in range(256)]
+    assert sorted(mt[mt > 0].tolist()) == sorted(want) and mt.min() >= 0
+    assert len(want) - 256 * 256 == 256 * (284 + 256 + 263 + 256)
+    # the base call: the same map without the block2_bpnet section (what test_training_pack_index_maps checks)
+    mb = _index_map(L.sgn_train_pack_index, 0, 0, n=nt)
+    ub = np.bincount(mb[mb > 0], minlength=N_PARAMS + 1)
+    assert ub.max() == 1 and int((ub > 0).sum()) == 256 * (284 + 256 + 263 + 256)
+    assert np.array_equal(mb, np.where(mt <= N_PARAMS, mt, 0))
+    # the base layout is a prefix of every variant's
+    for which, n in ((0, int(L.sgn_mlp_section(0)) // 2), (1, 2056), (2, (base - int(L.sgn_mlp_section(1))) // 2)):
+        assert np.array_equal(_index_map(L.sgn_mlp_pack_index, 1, dim, which, n=n),
+                              _index_map(L.sgn_mlp_pack_index, 0, 0, which, n=n))
+    # the block2_bpnet maps exist for the SG variants only
+    assert L.sgn_mlp_pack_index(0, 0, 3, (ctypes.c_int32 * 4)(), 4) != 0
+
+
+def test_merged_entry_argument_errors():
+    """The entries that take (bpnet_layers, bpnet_dim): an unsupported variant, a missing SG buffer and a
+    half-given projection list are argument errors, reported before any HIP call."""
+    L = _lib.lib()
+    fake = ctypes.c_void_p(16)
+    pt, qo = _lib.PointTables(), _lib.QueryOut()
+    for f in ("xyz", "embedding", "color", "dir", "conf", "campos", "camrotc2w", "raydir"):
+        setattr(pt, f, 16)
+    pt.n_points = 64
+    saved = _lib.AggSaved(16, 16, 16, 16)
+    deltas = _lib.AggDeltas(16, 16, 16, 16, 16, 16)
+    grads = _lib.PointGrads(16, 16, 16, 16)
+    P, Q, S, D, G = (ctypes.byref(x) for x in (pt, qo, saved, deltas, grads))
+    out = (ctypes.c_int32 * 4)()
+
+    def calls(nl, dim, h2b=fake, db=fake):
+        return {
+            "sgn_aggregate": lambda: L.sgn_aggregate(nl, dim, fake, None, P, Q, 64, 8, fake, fake, None, None, fake,
+                                                     1 << 20, 3, None),
+            "sgn_aggregate_train_fwd": lambda: L.sgn_aggregate_train_fwd(nl, dim, fake, P, Q, 64, 8, fake, fake, fake, S,
+                                                                         h2b, None),
+            "sgn_aggregate_backward": lambda: L.sgn_aggregate_backward(nl, dim, P, Q, 64, 8, fake, fake, S, h2b, fake,
+                                                                       fake, fake, D, db, G, None),
+            "sgn_aggregate_train_fwd_f32": lambda: L.sgn_aggregate_train_fwd_f32(nl, dim, fake, fake, P, Q, 64, 8, fake,
+                                                                                 fake, fake, fake, fake, fake, None, fake,
+                                                                                 1 << 20, None),
+            "sgn_mlp_pack_index": lambda: L.sgn_mlp_pack_index(nl, dim, 0, out, 4),
+            "sgn_train_pack_index": lambda: L.sgn_train_pack_index(nl, dim, out, 4),
+        }
+    for nl, dim in ((2, 96), (2, 0), (1, 32)):
+        for name, call in calls(nl, dim).items():
+            assert call() != 0 and b"block2_bpnet" in L.sgn_last_error(), (name, nl, dim)
+    for name in ("sgn_aggregate_train_fwd", "sgn_aggregate_backward"):
+        assert calls(1, 96, h2b=None)[name]() != 0 and b"null" in L.sgn_last_error(), name
+    assert calls(1, 96, db=None)["sgn_aggregate_backward"]() != 0 and b"null" in L.sgn_last_error()
+    assert calls(1, 0, db=None)["sgn_aggregate_backward"]() != 0 and b"null" in L.sgn_last_error()
+    for project in (L.sgn_point_project, L.sgn_point_project_f32):
+        assert project(P, fake, fake, None, fake, None) != 0 and b"d_idx and d_count" in L.sgn_last_error()
+        assert project(P, fake, None, fake, fake, None) != 0 and b"d_idx and d_count" in L.sgn_last_error()

@@ -676,3 +676,51 @@ def test_frame_points_lists_the_named_points(n_points, S, K):
         assert torch.equal(torch.sort(lst[:n].long().cpu()).values, want)
         assert int(cnt[1].item()) == (frame + 1 if n_points > 10 else 0)
         assert int(marks.count_nonzero().item()) == 0
+
+
+@pytest.mark.parametrize("n", [5, 1001])   # less than one tile; no multiple of the 32- / 16 * NW16-point tile
+@pytest.mark.parametrize("prec", ["f16", "f32"])
+def test_point_project_list(prec, n):
+    """sgn_point_project(_f32) over a device list: a permutation of every index equals the NULL / NULL
+    call byte for byte, a strict subset writes its rows only, a zero count writes nothing."""
+    import ctypes
+
+    from sgnerf_amd import _lib
+    from sgnerf_amd.weights import pack_mlp
+    L = _lib.lib()
+    f32 = prec == "f32"
+    g = torch.Generator().manual_seed(n)
+    tab = {k: (0.3 * torch.randn(n, w, generator=g)).to(DEV) for k, w in
+           (("xyz", 3), ("embedding", 32), ("color", 3), ("dir", 3), ("conf", 1))}
+    pt = _lib.PointTables()
+    for k, t in tab.items():
+        setattr(pt, k, t.data_ptr())
+    pt.n_points = n
+    packed = pack_mlp(init_mlp(0), DEV, prec)
+    project = L.sgn_point_project_f32 if f32 else L.sgn_point_project
+    nbytes = int((L.sgn_point_proj_bytes_f32 if f32 else L.sgn_point_proj_bytes)(n))
+    rec = 64 if f32 else 0                    # f32: a 64-B record per point after the P rows
+    row = nbytes // n - rec
+    FILL = 0xA5
+
+    def run(idx=None, count=None):
+        proj = torch.full((nbytes,), FILL, dtype=torch.uint8, device=DEV)
+        cnt = None if count is None else torch.tensor([count], dtype=torch.int64, device=DEV)
+        _lib.check(project(ctypes.byref(pt), _lib.ptr(packed), _lib.ptr(idx), _lib.ptr(cnt), _lib.ptr(proj),
+                           _lib.stream_handle()), "point projection")
+        torch.cuda.synchronize()
+        proj = proj.cpu()
+        return torch.cat([proj[:n * row].view(n, row), proj[n * row:].view(n, rec)], dim=1)   # per point
+
+    full = run()
+    assert bool((full != FILL).any(dim=1).all())            # every point's row written
+    perm = torch.randperm(n, generator=g).to(torch.int32)
+    assert torch.equal(run(perm.to(DEV), n), full)
+    part = perm[:n // 2]
+    out = run(part.to(DEV), part.numel())
+    listed = torch.zeros(n, dtype=torch.bool)
+    listed[part.long()] = True
+    assert 0 < int(listed.sum()) < n
+    assert torch.equal(out[listed], full[listed])
+    assert bool((out[~listed] == FILL).all())
+    assert bool((run(perm.to(DEV), 0) == FILL).all())

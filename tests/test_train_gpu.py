@@ -52,7 +52,7 @@ def test_device_pack_matches_host_pack():
     ref_t = torch.empty(int(L.sgn_train_tblob_bytes()), dtype=torch.uint8, device=DEV)
     ws = [np.ascontiguousarray(mlp[n + ".weight"].numpy()) for n, *_ in LAYERS[:4]]
     wp = (ctypes.c_void_p * 4)(*[w.ctypes.data for w in ws])
-    _lib.check(L.sgn_train_pack_t(wp, _lib.ptr(ref_t), _lib.stream_handle()), "sgn_train_pack_t")
+    _lib.check(L.sgn_train_pack_t(0, 0, wp, _lib.ptr(ref_t), _lib.stream_handle()), "sgn_train_pack_t")
     assert torch.equal(tblob.cpu(), ref_t.cpu())
 
 

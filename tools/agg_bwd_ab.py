@@ -1,5 +1,5 @@
 """Same-box A/B of k_agg_bwd builds (NOT product).  A few config-5 training steps (bench.py's
-train_main, f16) on the in-tree library record the last sgn_aggregate_backward[_sg] call; every
+train_main, f16) on the in-tree library record the last sgn_aggregate_backward call; every
 library named on the command line (tools/src_variant.sh builds) then replays that call between
 HIP events on the same stream, interleaved over rounds.  Before timing, each library's outputs of
 one replay (deltas, h4, dza bit for bit; point gradients to 1e-5 relative, atomics reorder) are
@@ -21,7 +21,7 @@ from sgnerf_amd import _lib  # noqa: E402
 
 sg = "--sg" in sys.argv
 libs = [a for a in sys.argv[1:] if not a.startswith("--")]
-NAME = "sgn_aggregate_backward_sg" if sg else "sgn_aggregate_backward"
+NAME = "sgn_aggregate_backward"
 rec = {}
 L0 = _lib.lib()
 
@@ -65,7 +65,7 @@ torch.cuda.set_device(dev)
 bench.train_main(args, 1, 0, dev, None)
 torch.cuda.synchronize()
 tr, a = rec["tr"], rec["args"]
-n = int(a[4 if sg else 2])
+n = int(a[4])   # (bpnet_layers, bpnet_dim, pt, q, n_items, ...)
 P = tr.points
 f16 = tr.stepper   # the F16Step's row buffers
 outs = [f16.d[0], f16.d[1], f16.d[2], f16.d[3], f16.h4, f16.dza] + ([f16.db] if sg else [])

@@ -1,7 +1,7 @@
 """Timing probe (not product): config-2 frames (tools/agg_time.py's setup, f32); for each frame the
 fraction of the 1.2 M points its samples touch, and HIP-event times of the full block1.0 point
 projection (sgn_point_project_f32) against the frame's point list (sgn_frame_points, the renderer's
-path) + the subset projection (sgn_point_project_f32_subset).   python tools/proj_touched.py [frames]"""
+path) + the projection of that list alone (sgn_point_project_f32 with d_idx).   python tools/proj_touched.py [frames]"""
 import ctypes
 import json
 import os
@@ -48,13 +48,13 @@ for i in range(2 + nf):
     pt.campos, pt.camrotc2w, pt.raydir = c.data_ptr(), rot.data_ptr(), rd.data_ptr()
     e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     e[0].record()
-    _lib.check(L.sgn_point_project_f32(ctypes.byref(pt), _lib.ptr(r.packed), _lib.ptr(r._proj), st), "full")
+    _lib.check(L.sgn_point_project_f32(ctypes.byref(pt), _lib.ptr(r.packed), None, None, _lib.ptr(r._proj), st), "full")
     e[1].record()
     _lib.check(L.sgn_frame_points(_lib.ptr(q.pidx), _lib.ptr(q.counters), q.pidx.numel() // 8, 8, N,
                                   _lib.ptr(marks), _lib.ptr(idx), _lib.ptr(cnt), st), "frame points")
     e[2].record()
-    _lib.check(L.sgn_point_project_f32_subset(ctypes.byref(pt), _lib.ptr(r.packed), _lib.ptr(idx),
-                                              _lib.ptr(cnt), _lib.ptr(r._proj), st), "subset")
+    _lib.check(L.sgn_point_project_f32(ctypes.byref(pt), _lib.ptr(r.packed), _lib.ptr(idx), _lib.ptr(cnt),
+                                       _lib.ptr(r._proj), st), "subset")
     e[3].record()
     torch.cuda.synchronize()
     if i >= 2:
