@@ -1067,6 +1067,7 @@ __global__ __launch_bounds__(TPB) void k_colour_head(RowArgs a, const float *h3,
     }
 }
 
+// (tests/test_train_rows_gpu.py sizes its grid-stride cases by HEAD_BLOCKS, ROW_HEAD_BLOCKS and ROW_GRID: P_*)
 constexpr int HEAD_BLOCKS = 256;
 // k_row_head's workgroups (its partials: [ROW_HEAD_BLOCKS][257], summed in a fixed order by k_reduce_wide):
 // 1024 took the head 132 -> 101 us per config-5 step (one wave walks ~4 items instead of ~15)
@@ -1491,12 +1492,17 @@ int sgn_x3_gemm(const sgn_x3_gemm_args *ga, sgn_stream_t stream) {
         const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
         k.splits = g.splits;
         const dim3 grid(nbm * nbn * g.splits);
+        // k_x3dw streams B in whole column quads and zeroes whole quads past ncols only: a column at or past
+        // ncols inside B's last quad would carry what memory holds there, so it must be the ones column or lie
+        // past N (every training-step shape); any other shape goes to k_x3tn, which zeroes per column
+        bool dw_quads = true;
+        for (int c = g.b.ncols; c < g.N && c < (g.b.ncols + 3) / 4 * 4; ++c) dw_quads = dw_quads && c == g.b.ones_col;
         if (p1) {
             SGN_REQUIRE(BM == 128 && (BN == 160 || BN == 96), "products 1: the colour layers' shapes (M <= 128, N > 32)");
             if (BN == 160) hipLaunchKernelGGL((k_x3tn<1, 5, true>), grid, dim3(TPB), 0, st, k);
             else hipLaunchKernelGGL((k_x3tn<1, 3, true>), grid, dim3(TPB), 0, st, k);
         } else if (BM == 256 && BN == 96 && g.M == 256 && !g.a.p2 && g.a.ones_col < 0 && !g.a.act && g.a.ncols >= 256 &&
-                   g.a.ld >= 256) {
+                   g.a.ld >= 256 && dw_quads) {
             // the row layers' weight gradients
             if (g.b.act) hipLaunchKernelGGL(k_x3dw<true>, grid, dim3(DW_TPB), 0, st, k);
             else hipLaunchKernelGGL(k_x3dw<false>, grid, dim3(DW_TPB), 0, st, k);
@@ -1541,7 +1547,7 @@ sgn::tx::RowArgs row_args(const sgn_point_tables *pt, const sgn_query_out *q, in
 }
 // one wave per work item, grid-stride: 16 waves per CU (4096 x 4) keep enough items' dependent load chains
 // in flight (1024 workgroups: k_row_inputs 153 -> 138 us, k_row_tail 88 -> 61 us per config-5 step)
-constexpr int ROW_GRID = 4096;
+constexpr int ROW_GRID = 4096;   // tests/test_train_rows_gpu.py: P_INPUTS = 8 ROW_GRID, P_ROWGRID = 4 ROW_GRID
 }  // namespace
 
 int sgn_train_row_inputs(const sgn_point_tables *pt, const sgn_query_out *q, int32_t K, const int32_t *d_row_off,
