@@ -18,7 +18,8 @@
 // torch.sin does (networks.py:175-192).  dtype of this path: "f32 (3xf16 split MFMA, fp32
 // accumulate)"; 3 MFMAs per product, so its MFMA ceiling is 1/3 of the fp16 dense peak.
 //
-// Kernels (v_mfma_f32_16x16x32_f16, 8 waves per 512-thread workgroup, two per SIMD):
+// Kernels (v_mfma_f32_16x16x32_f16; 8 waves per 512-thread workgroup, two per SIMD, except k_rows16's
+// 4 waves per 256-thread workgroup):
 //   k_point_proj16 : P[p] = 2^s0 (W0a [feat | PE(feat)] + b0) fp32 [256] + the packed 64-B point
 //                    record, once per point-cloud version
 //   k_pair_slots   : packs two samples whose neighbour counts sum to <= 8 into one 8-row half
@@ -26,8 +27,9 @@
 //                    P[pid], block1.2, (block2_bpnet), block3.0, block3.2 (transposed), alpha,
 //                    K-blend -> f_s fp32
 //   k_color16      : 8 waves x 16 samples: [f_s | PE(viewdir)] -> 128 -> 128 -> 128 -> 3, sigmoid
-// Weight fragment pairs (hi, lo) stream through a 2-slot LDS ring of 64-KiB chunks filled by
-// LDS-DMA, shared by the workgroup's 8 waves.
+// Weight fragment pairs (hi, lo) stream through a 2-slot LDS ring filled by LDS-DMA and shared by the
+// workgroup's waves: 64-KiB slots for the 8 waves of k_point_proj16 and k_color16, 32-KiB slots for
+// the 4 waves of a k_rows16 workgroup.
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -44,9 +46,7 @@ namespace x3 {
 
 constexpr int NW16 = 8, TPB16 = NW16 * 64;
 constexpr int PAIR = 2048;        // hi fragment (1 KiB) then lo fragment (1 KiB)
-constexpr int SLOT_PAIRS = 32;
-constexpr int SLOT = SLOT_PAIRS * PAIR;  // 64 KiB
-constexpr int NSLOT = 2;
+constexpr int NSLOT = 2;          // ring slots, each of a network's SP fragment pairs
 constexpr int PD = 2;     // fragment pairs in flight per wave (LDS -> VGPR queue)
 constexpr size_t PROJ_BYTES_PER_POINT = HID * 4;  // P row: fp32 [256], natural unit order
 struct XL {
@@ -71,32 +71,14 @@ struct Sched {
     }
     static constexpr int pairs(int n) { return nk(Net::L[cl(n)], cc(n)) * Net::L[cl(n)].tp; }
 };
-struct X3B {
-    h8 hi, lo;
-};
 
-// x -> (hi, lo): hi = fp16(x), lo = fp16(x - hi) (the difference is exact in fp32)
-__device__ __forceinline__ X3B split8(const float (&v)[8]) {
-    const X3Pair p = split8_unit(v);
-    return X3B{p.hi, p.lo};
-}
-
-// LeakyReLU(0.01) exactly as the reference (x, or fp32(0.01 x) below zero): max(x, 0.01 x) as one
-// v_max_f32 in inline asm -- fmaxf on an MFMA result makes the compiler canonicalise the operand with an
-// extra v_max_f32 x, x, x first (IEEE mode); NaN / inf still propagate (the fp16-range guard).  The asm
-// writes into the register of 0.01 x ("+v", tied; see split8_unit for why)
-__device__ __forceinline__ float lrelu_x3(float a) {
-    float r = 0.01f * a;
-    asm("v_max_f32 %0, %1, %0" : "+v"(r) : "v"(a));
-    return r;
-}
 // LeakyReLU(2^-s a) as the next layer's (hi, lo) fragment (LeakyReLU commutes with the exact
 // power-of-two scaling)
-__device__ __forceinline__ X3B lrelu_split8(const float (&a)[8], float inv) {
+__device__ __forceinline__ X3Pair lrelu_split8(const float (&a)[8], float inv) {
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = lrelu_x3(a[j] * inv);
-    return split8(v);
+    return split8_unit(v);
 }
 
 // one 1-KiB LDS-DMA piece of wave w: 16 B per lane from blob byte offset soff + w * 1024 + lane * 16 into
@@ -112,7 +94,7 @@ __device__ __forceinline__ void lds_dma_1k(const WBlob &wb, char *dst, int w, in
 // LDS-DMA of stream chunk N into `dst`: 2 * pairs 1-KiB pieces, wave w (of NWv) moves pieces
 // w + NWv j
 template <class Net, int N, int NWv = NW16>
-__device__ __forceinline__ void dma_chunk(const WBlob &wb, char *dst, int w, int lane, int) {
+__device__ __forceinline__ void dma_chunk(const WBlob &wb, char *dst, int w, int lane) {
     using S = Sched<Net>;
     constexpr int nf = 2 * S::pairs(N);
     static_for<(nf + NWv - 1) / NWv>([&](auto jj) {
@@ -128,7 +110,7 @@ __device__ __forceinline__ void dma_chunk(const WBlob &wb, char *dst, int w, int
 // (0 .. 3 KiB, applied to the blob address and the LDS address alike) steps through them: one s_mov pair per
 // four pieces instead of per piece (the initial dma_chunk keeps the interleaved assignment)
 template <class Net, int N, int J, int NWv = NW16>
-__device__ __forceinline__ void dma_piece(const WBlob &wb, char *dst, int w, int lane, int) {
+__device__ __forceinline__ void dma_piece(const WBlob &wb, char *dst, int w, int lane) {
     using S = Sched<Net>;
     constexpr int nf = 2 * S::pairs(N);
     constexpr int PW = (nf + NWv - 1) / NWv;
@@ -144,18 +126,14 @@ __device__ __forceinline__ void dma_piece(const WBlob &wb, char *dst, int w, int
 template <class Net, int N, int NWv = NW16>
 constexpr int dma_pieces() { return (2 * Sched<Net>::pairs(N) + NWv - 1) / NWv; }
 
-__device__ __forceinline__ int cur_slot(int s) { return s; }
-__device__ __forceinline__ int dma_slot(int s) { return s ^ 1; }
-__device__ __forceinline__ void chunk_exit(int &s, int) { s ^= 1; }
-
-// chunk boundary: this wave's DMAs of chunk N landed, LDS reads drained, barrier; then chunk N+1
-// goes into the slot every wave finished reading one chunk ago (its pieces are spread over the
-// chunk's MFMAs by run_layer16)
+// chunk boundary: this wave's DMAs of the chunk being entered landed, LDS reads drained, barrier; then
+// the next chunk goes into the slot every wave finished reading one chunk ago (its pieces are spread
+// over the chunk's MFMAs by run_layer_ns)
 // VM: vector-memory operations this wave is guaranteed to have issued after its last DMA piece of
 // the chunk being entered (loads placed at the end of the previous chunk, stores): they may stay in
 // flight across the boundary (vmcnt retires in order, so the DMA has landed once at most VM remain)
-template <class Net, int N, int NWv = NW16, int VM = 0>
-__device__ __forceinline__ void chunk_enter(const WBlob &, char *, int, int, int, int) {
+template <int VM = 0>
+__device__ __forceinline__ void chunk_enter() {
     static_assert(VM >= 0 && VM < 64, "vmcnt range");
     if constexpr (VM == 0)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -174,12 +152,6 @@ struct VmZero {
     static constexpr int vm(int) { return 0; }
 };
 
-
-// accurate sin/cos of x 2^F (the scaling is exact; torch.sin on the product, networks.py:186)
-template <int F>
-__device__ __forceinline__ void sincos_f(float x, float &s, float &c) {
-    sincos_acc(x * (float)(1 << F), s, c);
-}
 // =====================================================================================
 // 2 waves per SIMD: v_mfma_f32_16x16x32_f16, 8 waves x 16 rows (2 samples x K = 8) per
 // 128-row workgroup tile.  A wave's registers hold 16 rows (hi/lo layer input 64, all 16 output
@@ -191,8 +163,7 @@ __device__ __forceinline__ void sincos_f(float x, float &s, float &c) {
 // vectors.  Chained layers: k-step s of the next layer takes tiles 2s, 2s+1 of this one as
 // element j <- unit 16 (j >> 2) + 4 g + (j & 3) (perm16, folded into the packed weights).
 // =====================================================================================
-constexpr uint32_t OFF16_BASE = 0;
-constexpr uint32_t OFF16_W0B = OFF16_BASE;                  // block1.0 PE(dists): 2 ks x 16 tiles
+constexpr uint32_t OFF16_W0B = 0;                           // block1.0 PE(dists): 2 ks x 16 tiles
 constexpr uint32_t OFF16_W1 = OFF16_W0B + 32 * PAIR;        // block1.2: 8 x 16
 constexpr uint32_t OFF16_W2 = OFF16_W1 + 128 * PAIR;        // block3.0: 9 x 16
 constexpr uint32_t OFF16_W3 = OFF16_W2 + 144 * PAIR;        // block3.2: 8 x 16 (transposed use)
@@ -211,50 +182,44 @@ constexpr size_t BLOB_BYTES_ALL = OFF16_F32 + (size_t)N_Y32 * 4;
 __host__ __device__ constexpr size_t blob_bytes_sg(int) { return BLOB_BYTES_ALL; }
 static_assert(N_Y32 % 4 == 0, "fp32 section in 16-B units");
 
-// block3.2 in two passes of 8 output tiles: pass 0 converts the input once and keeps it
-// as (hi, lo) fragments, and the epilogue (K-blend, alpha) of its 8 tiles runs between pass 1's MFMAs
-// Row kernel workgroup (4 waves): 4 waves (one per SIMD) with a 2 x 32-KiB ring, so two
-// workgroups share a CU and their waves pair up on each SIMD without a common barrier (the barrier
-// of one chunk boundary no longer holds the other workgroup's wave of the SIMD: while one runs its
-// tile transition or epilogue VALU, the other's MFMAs keep the matrix pipe busy)
-constexpr int NWR = 4;                            // row waves
-constexpr int NSLR = NSLOT;                       // row ring slots
-static_assert(NWR == 4, "row workgroup: 4 waves");
-// ring slot of SP fragment pairs: 16 (NS = 1, two workgroups per CU) or 32 (NS = 2, one per CU);
-// KC = SP / 16 k-steps of 16 tiles per chunk
-template <int SP_>
+// Row kernel workgroup: 4 waves, one per SIMD, sharing a ring of 2 x 32 KiB (SP = 16 fragment pairs
+// per slot, one k-step of 16 tiles per chunk) for both NS.  NS = 1 (the save mode) is launched with two
+// workgroups per CU: their waves pair up on each SIMD without a common barrier (the barrier of one
+// chunk boundary does not hold the other workgroup's wave of the SIMD: while one runs its tile
+// transition or epilogue VALU, the other's MFMAs keep the matrix pipe busy).  NS = 2 (inference)
+// runs one workgroup per CU, one wave per SIMD, each weight fragment pair feeding two row sets.
+// block3.2 runs in two passes of 8 output tiles: pass 0 converts the input once and keeps it as
+// (hi, lo) fragments, and the epilogue (K-blend, alpha) of its 8 tiles runs between pass 1's MFMAs.
+constexpr int NWR = 4;  // row waves
 struct NetR16T {
-    static constexpr int NW = NWR, SP = SP_;  // waves sharing the ring, fragment pairs per ring slot
-    static constexpr int KC = SP_ / 16;
+    static constexpr int NW = NWR, SP = 16;  // waves sharing the ring, fragment pairs per ring slot
+    static constexpr int KC = SP / 16;       // k-steps of 16 tiles per chunk
     static constexpr int NL = 4;
     static constexpr XL L[NL] = {{2, 16, 1, KC, OFF16_W0B}, {8, 16, 1, KC, OFF16_W1}, {9, 16, 1, KC, OFF16_W2},
                                  {8, 8, 2, 2 * KC, OFF16_W3}};
 };
-template <int KB, int SP_>
+template <int KB>
 struct NetR16SGT {
-    static constexpr int NW = NWR, SP = SP_;
-    static constexpr int KC = SP_ / 16;
+    static constexpr int NW = NetR16T::NW, SP = NetR16T::SP, KC = NetR16T::KC;
     static constexpr int NL = 5;
     static constexpr XL L[NL] = {{2, 16, 1, KC, OFF16_W0B}, {8, 16, 1, KC, OFF16_W1}, {KB, 16, 1, KC, OFF16_WB},
                                  {9, 16, 1, KC, OFF16_W2}, {8, 8, 2, 2 * KC, OFF16_W3}};
 };
 struct NetProj16 {
-    static constexpr int NW = NW16, SP = SLOT_PAIRS;
+    static constexpr int NW = NW16, SP = 32;  // 64-KiB ring slots
     static constexpr int NL = 1;
     static constexpr XL L[NL] = {{7, 16, 1, 2, OFF16_W0A}};
 };
-// colour kernel workgroup (8 waves), as the row kernel's
-constexpr int NWC = 8, SPC = NWC == 4 ? 16 : 32, KCC = SPC / 8;
-static_assert(NWC == 4 || NWC == 8, "colour workgroup: 4 or 8 waves");
+// colour kernel workgroup: 8 waves (two per SIMD, one workgroup per CU), 64-KiB ring slots, four
+// k-steps of 8 tiles per chunk
+constexpr int NWC = 8, SPC = 32, KCC = SPC / 8;
 struct NetColor16 {
     static constexpr int NW = NWC, SP = SPC;
     static constexpr int NL = 3;
     static constexpr XL L[NL] = {{9, 8, 1, KCC, OFF16_C0}, {4, 8, 1, KCC, OFF16_C1}, {4, 8, 1, KCC, OFF16_C2}};
 };
-static_assert(Sched<NetR16T<16>>::total() == 27 && Sched<NetR16T<32>>::total() == 14 &&
-                  Sched<NetR16T<32>>::pairs(9) == 16, "16x16 row stream");
-static_assert(NWC == 4 ? Sched<NetColor16>::total() == 9 && Sched<NetColor16>::pairs(4) == 8
-                       : Sched<NetColor16>::total() == 5 && Sched<NetColor16>::pairs(2) == 8, "16x16 colour stream");
+static_assert(Sched<NetR16T>::total() == 27, "16x16 row stream");
+static_assert(Sched<NetColor16>::total() == 5 && Sched<NetColor16>::pairs(2) == 8, "16x16 colour stream");
 
 __device__ __forceinline__ f32x4 mfma16(h8 a, h8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
@@ -263,7 +228,7 @@ __device__ __forceinline__ f32x4 mfma16(h8 a, h8 b, f32x4 c) {
 // the B fragments of one k-step for NS row sets of 16 rows each
 template <int NS>
 struct X3S {
-    X3B b[NS];
+    X3Pair b[NS];
 };
 
 // One layer, k-outer over all output tiles of pass P: acc[s][AOFF + t] += W[t] in(k).b[s], three MFMAs
@@ -277,8 +242,8 @@ struct X3S {
 // conversion VALU.  Per pair the lo fragment (read after hi) feeds the first MFMA, so one lgkmcnt wait
 // covers both fragments.
 template <class Net, int L, bool TRANS = false, class Vm = VmZero, int P = 0, int AOFF = 0, bool PIPE = false,
-          int NS, int NA, class SlotT, class InFn, class PostFn = NoHook, class EndFn = NoHook, class MidFn = NoHook>
-__device__ __forceinline__ void run_layer_ns(const WBlob &wb, char *lds, SlotT &slot, int w, int lane, int lz,
+          int NS, int NA, class InFn, class PostFn = NoHook, class EndFn = NoHook, class MidFn = NoHook>
+__device__ __forceinline__ void run_layer_ns(const WBlob &wb, char *lds, int &slot, int w, int lane,
                                              f32x4 (&acc)[NS][NA], InFn &&in, PostFn &&post = PostFn{},
                                              EndFn &&end = EndFn{}, MidFn &&mid = MidFn{}) {
     constexpr XL ly = Net::L[L];
@@ -292,10 +257,10 @@ __device__ __forceinline__ void run_layer_ns(const WBlob &wb, char *lds, SlotT &
         constexpr int N = Sched<Net>::idx(L, P, C), NN = (N + 1) % Sched<Net>::total();
         constexpr int NWv = Net::NW, SLOTv = Net::SP * PAIR;
         static_assert(nk(ly, C) * TP <= Net::SP, "chunk larger than a ring slot");
-        chunk_enter<Net, N, NWv, Vm::vm(C)>(wb, lds, slot, w, lane, lz);
+        chunk_enter<Vm::vm(C)>();
         post(cc);
-        const char *sl = lds + cur_slot(slot) * SLOTv;
-        char *dnext = lds + dma_slot(slot) * SLOTv;
+        const char *sl = lds + slot * SLOTv;
+        char *dnext = lds + (slot ^ 1) * SLOTv;
         constexpr int NF = nk(ly, C) * TP;
         constexpr int PW = dma_pieces<Net, NN, NWv>();
         auto frag = [&](int f, int part) { return *(const h8 *)(sl + (2 * f + part) * 1024 + lane * 16); };
@@ -338,7 +303,7 @@ __device__ __forceinline__ void run_layer_ns(const WBlob &wb, char *lds, SlotT &
                 constexpr int NSP = NF / 2 > 0 ? NF / 2 : 1;
                 if constexpr (F < NSP) {
                     static_for<(F + 1) * PW / NSP - F * PW / NSP>([&](auto jj) {
-                        dma_piece<Net, NN, F * PW / NSP + decltype(jj)::value, NWv>(wb, dnext, w, lane, lz);
+                        dma_piece<Net, NN, F * PW / NSP + decltype(jj)::value, NWv>(wb, dnext, w, lane);
                     });
                 }
                 mid(std::integral_constant<int, (C * ly.kc + KK) * TP + t>{});
@@ -361,36 +326,20 @@ __device__ __forceinline__ void run_layer_ns(const WBlob &wb, char *lds, SlotT &
         });
         __builtin_amdgcn_sched_barrier(0);
         end(cc);  // after every DMA piece of the chunk: loads here may stay in flight one boundary
-        chunk_exit(slot, lane);
+        slot ^= 1;
         __builtin_amdgcn_sched_barrier(0);
     });
 }
 
 // one row set (16 rows / units of the accumulators): the layer loop above with NS = 1
-template <class Net, int L, bool TRANS = false, class Vm = VmZero, int P = 0, class SlotT, class InFn,
+template <class Net, int L, bool TRANS = false, class Vm = VmZero, int P = 0, class InFn,
           class PostFn = NoHook, class EndFn = NoHook, class MidFn = NoHook>
-__device__ __forceinline__ void run_layer16(const WBlob &wb, char *lds, SlotT &slot, int w, int lane, int lz,
+__device__ __forceinline__ void run_layer16(const WBlob &wb, char *lds, int &slot, int w, int lane,
                                             f32x4 (&acc)[Net::L[L].tp], InFn &&in, PostFn &&post = PostFn{},
                                             EndFn &&end = EndFn{}, MidFn &&mid = MidFn{}) {
     constexpr int TP = Net::L[L].tp;
-    run_layer_ns<Net, L, TRANS, Vm, P, 0>(wb, lds, slot, w, lane, lz, reinterpret_cast<f32x4(&)[1][TP]>(acc),
+    run_layer_ns<Net, L, TRANS, Vm, P, 0>(wb, lds, slot, w, lane, reinterpret_cast<f32x4(&)[1][TP]>(acc),
                                           [&](auto k) { return X3S<1>{{in(k)}}; }, post, end, mid);
-}
-
-// LeakyReLU(2^-s acc + add) of 16 tiles -> the next layer's 8 k-step B fragments (hi/lo)
-template <bool ADD>
-__device__ __forceinline__ void chain_out16(const f32x4 (&acc)[16], const f32x4 (&add)[16], float inv, X3B (&out)[8]) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float a = acc[2 * s + (j >> 2)][j & 3];
-            const float y = ADD ? (a + add[2 * s + (j >> 2)][j & 3]) * inv : a * inv;
-            v[j] = fmaxf(y, 0.01f * y);
-        }
-        out[s] = split8(v);
-    }
 }
 
 // ---- per-point block1.0 projection (16x16): P[p] fp32 [256] in natural unit order ----
@@ -405,7 +354,7 @@ struct Proj16Args {
     const int64_t *n_dev;  // device count of idx (<= n)
 };
 constexpr int REC16_FLOATS = 16;
-constexpr int Y_LDS_OFF = NSLOT * SLOT;
+constexpr int Y_LDS_OFF = NSLOT * NetProj16::SP * PAIR;
 constexpr int PROJ16_LDS = Y_LDS_OFF + N_Y32 * 4;
 
 __global__ __launch_bounds__(TPB16, 1) void k_point_proj16(Proj16Args a) {
@@ -420,7 +369,7 @@ __global__ __launch_bounds__(TPB16, 1) void k_point_proj16(Proj16Args a) {
     }
     __syncthreads();
     int slot = 0;
-    dma_chunk<NetProj16, 0, NW16>(wb, lds, w, lane, 0);
+    dma_chunk<NetProj16, 0, NW16>(wb, lds, w, lane);
     const int64_t n = a.idx ? min(*a.n_dev, a.n) : a.n;
     const int64_t ntile = (n + 16 * NW16 - 1) / (16 * NW16);
     for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
@@ -458,7 +407,7 @@ __global__ __launch_bounds__(TPB16, 1) void k_point_proj16(Proj16Args a) {
                     v[2 * decltype(jp)::value + 1] = cv;
                 });
             }
-            return split8(v);
+            return split8_unit(v);
         };
         // the point's packed record, lane group g's 16-B quarter: loaded here, stored after the
         // MFMAs (which hide the loads)
@@ -468,7 +417,7 @@ __global__ __launch_bounds__(TPB16, 1) void k_point_proj16(Proj16Args a) {
             const int64_t pc = ok ? p : 0;
             if (g < 3) q = f32x4{src[pc * 3], src[pc * 3 + 1], src[pc * 3 + 2], g == 0 ? a.conf[pc] : 0.f};
         }
-        run_layer16<NetProj16, 0>(wb, lds + lz, slot, w, lane, lz, acc, in);
+        run_layer16<NetProj16, 0>(wb, lds + lz, slot, w, lane, acc, in);
         if (ok) {  // natural unit order: tile t of lane group g at 16 t + 4 g (64 B per point per store)
             float *dst = a.proj + p * HID + 4 * g;
 #pragma unroll
@@ -482,12 +431,12 @@ __global__ __launch_bounds__(TPB16, 1) void k_point_proj16(Proj16Args a) {
 // ---- per-neighbour rows (16x16) -------------------------------------------------------------
 constexpr int WG16_SAMPLES = NWR * 2;            // halves (16 rows, 2 per wave) per workgroup tile
 constexpr int TPBR = NWR * 64;
-// the row kernel's LDS: ring (NSLR slots of SP pairs), fp32 section, then [unit r][20] 2^s3 b3
+// the row kernel's LDS: ring (NSLOT slots of SP pairs), fp32 section, then [unit r][20] 2^s3 b3
 // (t = 0..15) and [r][20] 2^-s3 alpha w
-__host__ __device__ constexpr int yr_off(int sp) { return NSLR * sp * PAIR; }
-__host__ __device__ constexpr int yt16_off(int sp) { return yr_off(sp) + N_Y32 * 4; }
-__host__ __device__ constexpr int rows16_lds(int sp) { return yt16_off(sp) + 2 * 16 * 20 * 4; }
-static_assert(2 * rows16_lds(16) <= 163840, "LDS budget (16x16 rows)");
+constexpr int YR_OFF = NSLOT * NetR16T::SP * PAIR;
+constexpr int YT16_OFF = YR_OFF + N_Y32 * 4;
+constexpr int ROWS16_LDS = YT16_OFF + 2 * 16 * 20 * 4;
+static_assert(2 * ROWS16_LDS <= 163840, "LDS budget (16x16 rows, two workgroups per CU)");
 
 // row r's point record, its sample position and view direction (+ the caller's pers
 // coordinates on the compatibility path)
@@ -771,7 +720,7 @@ __device__ __forceinline__ float pe_arg16(const PeRow &r) {
 // second k-step's sin / cos overlap the first one's MFMAs).  Arguments of 2^20 and above (never met
 // by the aggregator's distances) take the library sincosf, behind one wave-uniform branch.
 template <int S>
-__device__ __forceinline__ X3B pe_dists16_k(const PeRow &r) {
+__device__ __forceinline__ X3Pair pe_dists16_k(const PeRow &r) {
     float x[4], u[8];
     static_for<4>([&](auto cc) { x[decltype(cc)::value] = pe_arg16<4 * S + decltype(cc)::value>(r); });
     const float m = fmaxf(fmaxf(__builtin_fabsf(x[0]), __builtin_fabsf(x[1])), fmaxf(__builtin_fabsf(x[2]), __builtin_fabsf(x[3])));
@@ -782,7 +731,7 @@ __device__ __forceinline__ X3B pe_dists16_k(const PeRow &r) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) sincos_acc_fast(x[q], u[2 * q], u[2 * q + 1]);
     }
-    return split8(u);
+    return split8_unit(u);
 }
 
 // block3.2 epilogue of a tile (K-blend -> f_s, alpha), per lane: rows 4 g + i of half g >> 1
@@ -809,10 +758,9 @@ __device__ __forceinline__ Tiles grid_tiles(int ntiles) { return Tiles{(int)bloc
 // NS: row sets of 16 rows per wave.  NS = 2: 32 rows per wave, each LDS weight fragment pair feeds
 // six MFMAs (half the LDS reads and weight DMA per MFMA of NS = 1), one workgroup per CU and one
 // wave per SIMD (the accumulators of two layers, 256 registers, sit in AGPRs)
-template <int KB, bool PERS, bool SAVE = false, int NS = 1, int SP = 16>
+template <int KB, bool PERS, bool SAVE = false, int NS = 1>
 __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs a) {
-    using Net = std::conditional_t<(KB > 0), NetR16SGT<KB, SP>, NetR16T<SP>>;
-    constexpr int YR_OFF = yr_off(SP), YT16_OFF = yt16_off(SP), ROWS16_LDS = rows16_lds(SP);
+    using Net = std::conditional_t<(KB > 0), NetR16SGT<KB>, NetR16T>;
     constexpr int LB = 2, L2 = KB ? 3 : 2, L3 = KB ? 4 : 3;
     constexpr int NBP = KB > 8 ? KB - 8 : 0;  // BPNet k-steps (32 channels each)
     constexpr int WGS = WG16_SAMPLES * NS;    // halves per workgroup tile
@@ -839,7 +787,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
     }
     __syncthreads();
     int slot = 0;
-    dma_chunk<Net, 0, NWR>(wb, lds, w, lane, 0);
+    dma_chunk<Net, 0, NWR>(wb, lds, w, lane);
     // The next tile's chain, prefetched inside the current tile so each step lands under MFMAs:
     // row-table entry (block1.2), neighbour / ray index (block3.0), point record + sample position
     // and the P row (block3.2).  First tile: here.  Row set q of wave w: halves w 2 NS + 2 q (+ sc).
@@ -872,9 +820,8 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
         for (int i = 0; i < 4; ++i) {
             const float wi = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((4 * g + i) * 4, __builtin_bit_cast(int, wgt)));
             const bool inA = 4 * (g & 1) + i < nA;
-            const float ws = wi;
-            e.wsa[i] = inA ? ws : 0.f;
-            e.wsb[i] = inA ? 0.f : ws;
+            e.wsa[i] = inA ? wi : 0.f;
+            e.wsb[i] = inA ? 0.f : wi;
             e.ap[i] = 0.f;
         }
         e.fs_have = ((g & 1) ? nB > 0 : nA > 0) && ok;
@@ -951,7 +898,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
         int nslot[NS], nA[NS], nB[NS];
         uint64_t mrowA[NS], mrowB[NS];
         int64_t vrow[NS];
-        X3B ext[NS];
+        X3Pair ext[NS];
         const int hsh = 8 * (g >> 1);  // half g >> 1's row bits
 #pragma unroll
         for (int q = 0; q < NS; ++q) {
@@ -990,7 +937,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
                 u[6] = e ? __fadd_rn(__fadd_rn(__fmul_rn(rc.dir[0], rc.v[0]), __fmul_rn(rc.dir[1], rc.v[1])),
                                      __fmul_rn(rc.dir[2], rc.v[2])) : 0.f;
                 u[7] = 0.f;
-                ext[q] = split8(u);
+                ext[q] = split8_unit(u);
             }
         }
         // Each layer's epilogue (LeakyReLU + hi/lo split of its accumulators) runs lazily inside the
@@ -1025,7 +972,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
                 }
             }
             run_layer_ns<Net, 0, false, std::conditional_t<SAVE, VmZero, VmL0<NS>>, 0, 0, !SAVE>(
-                wb, ldsi, slot, w, lane, lz, accA, [&](auto k) {
+                wb, ldsi, slot, w, lane, accA, [&](auto k) {
                     X3S<NS> o;
 #pragma unroll
                     for (int q = 0; q < NS; ++q) o.b[q] = pe_dists16_k<decltype(k)::value>(pr[q]);
@@ -1037,7 +984,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
 #pragma unroll
         for (int q = 0; q < NS; ++q) bias_init(accB[q], Y_B1);
         int v_next[NS];
-        run_layer_ns<Net, 1, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, lz, accB, [&](auto k) {
+        run_layer_ns<Net, 1, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, accB, [&](auto k) {
             X3S<NS> o;
 #pragma unroll
             for (int q = 0; q < NS; ++q) o.b[q] = chain_k(q, accA[q], inv0, k, a.z1);
@@ -1051,7 +998,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
         if constexpr (KB > 0) {
             // block2_bpnet.0 (SG): [h 256 | BPNet embedding] -> 256; the row's fp32 embedding
             // (channels 32 m + 8 g .. +7 for k-step 8 + m) gathered and split here
-            X3B bpv[NS][NBP > 0 ? NBP : 1];
+            X3Pair bpv[NS][NBP > 0 ? NBP : 1];
             if constexpr (NBP > 0) {
 #pragma unroll
                 for (int q = 0; q < NS; ++q) {
@@ -1060,13 +1007,13 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
                     for (int j = 0; j < NBP; ++j) {
                         const f32x4 u0 = *(const f32x4 *)(src + 32 * j), u1 = *(const f32x4 *)(src + 32 * j + 4);
                         const float v[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
-                        bpv[q][j] = split8(v);
+                        bpv[q][j] = split8_unit(v);
                     }
                 }
             }
 #pragma unroll
             for (int q = 0; q < NS; ++q) bias_init(accA[q], Y_BB);
-            run_layer_ns<Net, LB>(wb, ldsi, slot, w, lane, lz, accA, [&](auto k) {
+            run_layer_ns<Net, LB>(wb, ldsi, slot, w, lane, accA, [&](auto k) {
                 constexpr int K = decltype(k)::value;
                 X3S<NS> o;
 #pragma unroll
@@ -1083,7 +1030,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
         const float inv_in2 = KB > 0 ? inv7 : inv1;
 #pragma unroll
         for (int q = 0; q < NS; ++q) bias_init(acc2[q], Y_B2);
-        run_layer_ns<Net, L2, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, lz, acc2, [&](auto k) {
+        run_layer_ns<Net, L2, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, acc2, [&](auto k) {
             constexpr int K = decltype(k)::value;
             X3S<NS> o;
 #pragma unroll
@@ -1135,9 +1082,9 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
             // pass 0 (output tiles 0..7) converts block3.0's output once into (hi, lo) fragments (in the
             // registers it frees) and pass 1 (tiles 8..15) reuses them; pass 1 carries the epilogue of
             // pass 0's tiles, output tile T after k-step T (one per 8 MFMA pairs)
-            X3B in3[NS][8];
+            X3Pair in3[NS][8];
             run_layer_ns<Net, L3, true, std::conditional_t<SAVE, VmZero, VmL3P0<NS>>, 0, 0, !SAVE>(
-                wb, ldsi, slot, w, lane, lz, acc, [&](auto k) {
+                wb, ldsi, slot, w, lane, acc, [&](auto k) {
                     constexpr int K = decltype(k)::value;
                     X3S<NS> o;
 #pragma unroll
@@ -1149,7 +1096,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
                 }, NoHook{}, first_chunk_loads);
 #pragma unroll
             for (int q = 0; q < NS; ++q) epi_begin(e[q], ldsi, rw[q].wgt, nA[q], nB[q], ce[q], eslot[q] < nslots);
-            run_layer_ns<Net, L3, true, VmZero, 1, 8>(wb, ldsi, slot, w, lane, lz, acc, [&](auto k) {
+            run_layer_ns<Net, L3, true, VmZero, 1, 8>(wb, ldsi, slot, w, lane, acc, [&](auto k) {
                 X3S<NS> o;
 #pragma unroll
                 for (int q = 0; q < NS; ++q) o.b[q] = in3[q][decltype(k)::value];
@@ -1350,9 +1297,9 @@ struct ColorArgs {
 // plus two cross-group shuffles.
 constexpr int YC_OFF = NSLOT * SPC * PAIR, TPBC = NWC * 64;
 constexpr int COL16_LDS = YC_OFF + N_Y32 * 4;
-static_assert(COL16_LDS * (8 / NWC) <= 163840, "LDS budget (colour, 8 / NWC workgroups per CU)");
+static_assert(COL16_LDS <= 163840, "LDS budget (colour, one workgroup per CU)");
 
-__global__ __launch_bounds__(TPBC, 8 / NWC) void k_color16(ColorArgs a) {
+__global__ __launch_bounds__(TPBC, 1) void k_color16(ColorArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[COL16_LDS];
     const int lane = threadIdx.x & 63;
     const int g = lane >> 4, r = lane & 15;
@@ -1367,14 +1314,14 @@ __global__ __launch_bounds__(TPBC, 8 / NWC) void k_color16(ColorArgs a) {
     }
     __syncthreads();
     int slot = 0;
-    dma_chunk<NetColor16, 0, NWC>(wb, lds, w, lane, 0);
+    dma_chunk<NetColor16, 0, NWC>(wb, lds, w, lane);
     // The tile's f_s rows go out in four quarters (k-steps 2 q, 2 q + 1 of colour 0), each at a chunk
     // boundary after its registers were consumed and a chunk before they are needed: the next tile's
     // quarter 0 in colour 0's second chunk, quarter 1 (and the sample ids) in colour 1, quarter 2 (and
     // the ray ids) in colour 2, quarter 3 in the tile's own first chunk with its ray directions.  The
     // rows as one 16 KiB-per-wave burst had to land within one chunk (vmcnt retires in order: the next
     // boundary's wait for its weight pieces waits for them too), and did not (colour stage -23 % without
-    // them, tools/x3_variant.py cabl_fs).
+    // them, an ablation build).
     f32x4 fr[16];
     float vd[3];
     int sn = 0, rn = 0;
@@ -1433,7 +1380,7 @@ __global__ __launch_bounds__(TPBC, 8 / NWC) void k_color16(ColorArgs a) {
         };
         f32x4 c0[8], c1[8];
         bias(c0, Y_CB0);
-        run_layer16<NetColor16, 0>(wb, ldsi, slot, w, lane, lz, c0, [&](auto k) {
+        run_layer16<NetColor16, 0>(wb, ldsi, slot, w, lane, c0, [&](auto k) {
             constexpr int K = decltype(k)::value;
             float v[8];
             if constexpr (K < 8) {
@@ -1460,7 +1407,7 @@ __global__ __launch_bounds__(TPBC, 8 / NWC) void k_color16(ColorArgs a) {
                     for (int f = 0; f < 4; ++f) sincos_acc_fast(y[f], v[2 * f], v[2 * f + 1]);
                 }
             }
-            return split8(v);
+            return split8_unit(v);
         }, [&](auto c) {
             constexpr int C = decltype(c)::value;
             if constexpr (C == 0) {
@@ -1472,7 +1419,7 @@ __global__ __launch_bounds__(TPBC, 8 / NWC) void k_color16(ColorArgs a) {
         bias(c1, Y_CB1);
         const float inv4 = Yl[Y_INV + 4], inv5 = Yl[Y_INV + 5], inv6 = Yl[Y_INV + 6];
         // colour 0 consumed fr: the next tile's quarters 1, 2 go out at colour 1's and colour 2's boundaries
-        run_layer16<NetColor16, 1>(wb, ldsi, slot, w, lane, lz, c1, [&](auto k) { return chain(c0, inv4, k); },
+        run_layer16<NetColor16, 1>(wb, ldsi, slot, w, lane, c1, [&](auto k) { return chain(c0, inv4, k); },
                                    [&](auto c) {
                                        if constexpr (decltype(c)::value == 0) {
                                            load_q(std::integral_constant<int, 1>{}, item + gridDim.x * (16 * NWC));
@@ -1480,7 +1427,7 @@ __global__ __launch_bounds__(TPBC, 8 / NWC) void k_color16(ColorArgs a) {
                                        }
                                    });
         bias(c0, Y_CB2);
-        run_layer16<NetColor16, 2>(wb, ldsi, slot, w, lane, lz, c0, [&](auto k) { return chain(c1, inv5, k); },
+        run_layer16<NetColor16, 2>(wb, ldsi, slot, w, lane, c0, [&](auto k) { return chain(c1, inv5, k); },
                                    [&](auto c) {
                                        if constexpr (decltype(c)::value == 0) {
                                            load_q(std::integral_constant<int, 2>{}, item + gridDim.x * (16 * NWC));
@@ -1614,15 +1561,26 @@ size_t sgn_aggregate_workspace_bytes_f32(int64_t S) {
 }
 
 namespace {
+// work items a workspace of `workspace_bytes` holds
+int64_t ws_item_count(size_t workspace_bytes) {
+    return workspace_bytes > (size_t)WS_TAIL ? (int64_t)((workspace_bytes - WS_TAIL) / WS_PER_ITEM) : 0;
+}
 int32_t *ws_tail(void *d_workspace, size_t workspace_bytes) {
-    const int64_t ws_items = workspace_bytes > (size_t)WS_TAIL ? (int64_t)((workspace_bytes - WS_TAIL) / WS_PER_ITEM) : 0;
-    return (int32_t *)((char *)d_workspace + ws_items * WS_PER_ITEM);
+    return (int32_t *)((char *)d_workspace + ws_item_count(workspace_bytes) * WS_PER_ITEM);
 }
 }  // namespace
 
 }  // extern "C"
 
 namespace {
+// k_rows16 of a network variant: KB = block2_bpnet.0's k-steps (0: base, 8: bpnet_dim 0, 11: dim 96)
+template <bool PERS, bool SAVE, int NS>
+auto rows_kernel(int ksb) {
+    using namespace sgn;
+    return ksb == 0 ? x3::k_rows16<0, PERS, SAVE, NS> : ksb == mlp::KS_HID ? x3::k_rows16<8, PERS, SAVE, NS>
+                                                                            : x3::k_rows16<11, PERS, SAVE, NS>;
+}
+
 int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const void *d_point_proj,
                   const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
                   const void *d_packed, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
@@ -1642,7 +1600,7 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
     SGN_REQUIRE(S_capacity >= 0 && S_capacity < (1 << 30), "S_capacity out of range");
     SGN_REQUIRE(((uintptr_t)d_workspace & 15) == 0 && ((uintptr_t)d_point_proj & 15) == 0, "16-byte alignment required");
     hipStream_t st = as_stream(stream);
-    const int64_t ws_items = workspace_bytes > (size_t)WS_TAIL ? (int64_t)((workspace_bytes - WS_TAIL) / WS_PER_ITEM) : 0;
+    const int64_t ws_items = ws_item_count(workspace_bytes);
     SGN_REQUIRE(ws_items >= 32, "aggregate workspace too small");
     SGN_REQUIRE(stages == 3 || ws_items >= S_capacity,
                 "stages 1 and 2 called separately need a workspace for all S_capacity items");
@@ -1697,18 +1655,15 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
             // inference rows: 32 rows per wave (NS = 2; 0.94x the time of NS = 1 at config 2,
             // profiles/r04_v2_bench_rows_ns*.json); the save mode (training) keeps NS = 1
             const int ns = z ? 1 : 2;
-            auto kern = z ? (ksb == 0 ? x3::k_rows16<0, false, true> : ksb == KS_HID ? x3::k_rows16<8, false, true>
-                                                                                  : x3::k_rows16<11, false, true>)
-                          : pt->pers ? (ksb == 0 ? x3::k_rows16<0, true, false, 2> : ksb == KS_HID ? x3::k_rows16<8, true, false, 2>
-                                                                                      : x3::k_rows16<11, true, false, 2>)
-                                     : (ksb == 0 ? x3::k_rows16<0, false, false, 2> : ksb == KS_HID ? x3::k_rows16<8, false, false, 2>
-                                                                                        : x3::k_rows16<11, false, false, 2>);
+            auto kern = z ? rows_kernel<false, true, 1>(ksb)              // <PERS, SAVE, NS>
+                          : pt->pers ? rows_kernel<true, false, 2>(ksb)  // the caller's pers coordinates
+                                     : rows_kernel<false, false, 2>(ksb);
             const int64_t wg16 = (n + x3::WG16_SAMPLES * ns - 1) / (x3::WG16_SAMPLES * ns),
                           wmax = ns == 1 ? 256 * (8 / x3::NWR) : 256;
             hipLaunchKernelGGL(kern, dim3((unsigned)(wg16 < wmax ? wg16 : wmax)), dim3(x3::TPBR), 0, st, a);
         }
         if (stages & 2) {
-            const int64_t wgc = (n + 16 * x3::NWC - 1) / (16 * x3::NWC), wcmax = 256 * (8 / x3::NWC);
+            const int64_t wgc = (n + 16 * x3::NWC - 1) / (16 * x3::NWC), wcmax = 256;
             hipLaunchKernelGGL(x3::k_color16, dim3((unsigned)(wgc < wcmax ? wgc : wcmax)), dim3(x3::TPBC), 0, st, c);
         }
     }
@@ -1767,13 +1722,12 @@ int64_t sgn_mlp_layout_f32(int32_t which) {
 int64_t sgn_aggregate_fs_offset_f32(size_t workspace_bytes, int64_t S_capacity) {
     // aggregate_f32 keeps item i's f_s at d_workspace + i * 1 KiB when the workspace holds every item
     // (`full`), else it reuses the first rows chunk by chunk
-    const int64_t ws_items = workspace_bytes > (size_t)WS_TAIL ? (int64_t)((workspace_bytes - WS_TAIL) / WS_PER_ITEM) : 0;
+    const int64_t ws_items = ws_item_count(workspace_bytes);
     return S_capacity >= 0 && ws_items >= 32 && ws_items >= S_capacity ? 0 : -1;
 }
 
 size_t sgn_aggregate_flag_offset_f32(size_t workspace_bytes) {
-    const int64_t ws_items = workspace_bytes > (size_t)WS_TAIL ? (int64_t)((workspace_bytes - WS_TAIL) / WS_PER_ITEM) : 0;
-    return (size_t)(ws_items * WS_PER_ITEM + 4);
+    return (size_t)(ws_item_count(workspace_bytes) * WS_PER_ITEM + 4);
 }
 
 }  // extern "C"

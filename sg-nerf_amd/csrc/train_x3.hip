@@ -105,14 +105,6 @@ __device__ __forceinline__ int op_shift(const Opnd &o) {
     return 0;
 }
 
-__device__ __forceinline__ float lrelu_ref(float x) { return x > 0.f ? x : x * 0.01f; }
-// the same value as max(x, 0.01 x) in two instructions (one v_max: no canonicalising max of a loaded value)
-__device__ __forceinline__ float lrelu_max(float x) {
-    float t = x * 0.01f;
-    asm("v_max_f32 %0, %1, %0" : "+v"(t) : "v"(x));
-    return t;
-}
-
 // ---- split-K mode: C[m][n] = sum over rows r of A(m, r) B(n, r) ---------------------------------
 // Both operands are row-major [rows][cols] (kmajor).  A stage is 32 rows; thread t of an operand loads
 // 4 consecutive columns (a quad) of 8 consecutive rows (an octet) as 8 float4, which transpose in
@@ -158,7 +150,7 @@ __device__ __forceinline__ void load8(const Opnd &o, const OpRs &rs, int i, int 
         for (int e = 0; e < 8; ++e) {
             const int c = k + e;
             float u = c == o.ones_col ? (rok ? 1.f : 0.f) : c < o.ncols ? v[e] : 0.f;
-            if (o.act && s1 && c != o.ones_col) u = lrelu_ref(u);
+            if (o.act && s1 && c != o.ones_col) u = lrelu(u);
             v[e] = u;
         }
     } else {
@@ -173,7 +165,7 @@ __device__ __forceinline__ void load8(const Opnd &o, const OpRs &rs, int i, int 
             const float x1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs.r1, a1, 0, 0));
             const float x2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs.r2, a2, 0, 0));
             float u = i == o.ones_col ? (r < lim ? 1.f : 0.f) : cok ? (s1 ? x1 : x2) : 0.f;
-            if (o.act && s1 && cok) u = lrelu_ref(u);
+            if (o.act && s1 && cok) u = lrelu(u);
             v[e] = u;
         }
     }
@@ -210,7 +202,7 @@ struct QStage {
         if (o.act && s1) {
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                v[e] = make_float4(lrelu_ref(v[e].x), lrelu_ref(v[e].y), lrelu_ref(v[e].z), lrelu_ref(v[e].w));
+                v[e] = make_float4(lrelu(v[e].x), lrelu(v[e].y), lrelu(v[e].z), lrelu(v[e].w));
         }
         const bool spec = c + 4 > o.ncols || (o.ones_col >= c && o.ones_col < c + 4);
         if (__ballot(spec) != 0) {   // wave-uniform
@@ -603,7 +595,7 @@ struct ARow {
         v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
         if (ACT && s1) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = lrelu_max(v[e]);
+            for (int e = 0; e < 8; ++e) v[e] = lrelu_x3(v[e]);
         }
     }
 };
@@ -720,7 +712,7 @@ __global__ __launch_bounds__(RT_TPB, 1) void k_x3rows(GemmK g) {
                     const uint32_t rr = (r & 3) + 8 * (r >> 2);
                     float v = acc[t][r] * osc + bv;
                     if (g.mask && (!O2 || o1) && !(mk[r] > 0.f)) v *= 0.01f;
-                    const float v1 = g.act ? lrelu_max(v) : v;
+                    const float v1 = g.act ? lrelu_x3(v) : v;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v1), ro1, b1, rr * (uint32_t)g.ldo * 4, 0);
                     const bool rok = FULL || (int)(rb + rr) < rows;
                     am1 = fmaxf(am1, (!O2 || o1) && rok ? fabsf(v1) : 0.f);
@@ -1122,8 +1114,6 @@ __global__ __launch_bounds__(TPB) void k_colour_head_bwd(RowArgs a, const float 
     if (lane == 0) atomicMax(amax, __builtin_bit_cast(uint32_t, am));
 }
 
-__device__ __forceinline__ float softplus_ref(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-
 // block3.2's output and everything between it and the blended feature (point_aggregators.py:
 // 640-653, :743-770): h4 = LReLU(z4); alpha = softplus(wa h4 + ba - 1); f_s = sum_k w_k h4_k,
 // alpha_s = sum_k w_k alpha_k.  Backward per row: dza = w dalpha_s sigmoid(za - 1);
@@ -1183,7 +1173,7 @@ __global__ __launch_bounds__(TPB) void k_row_head(RowArgs a, float *z4d4, const 
             float pa = 0.f, pd = 0.f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float h = lrelu_ref(z[k][q]);
+                const float h = lrelu(z[k][q]);
                 pa += wa4[q] * h;
                 pd += h * df[q];
             }
@@ -1198,14 +1188,14 @@ __global__ __launch_bounds__(TPB) void k_row_head(RowArgs a, float *z4d4, const 
             const float za = lane_value(red[0], 4 * k) + bav;
             const float dot = lane_value(red[0], 4 * (MAX_K + k));
             const float x = za - 1.f;
-            const float al = softplus_ref(x), sg = x > 20.f ? 1.f : 1.f / (1.f + expf(-x));
+            const float al = softplus(x), sg = x > 20.f ? 1.f : 1.f / (1.f + expf(-x));
             const float wk = lane_value(wwl.x, k), wnk = lane_value(wwl.y, k);
             const float dza = wk * das * sg;
             const float dw = dot + al * das;
             f32x4 d;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float h = lrelu_ref(z[k][q]);
+                const float h = lrelu(z[k][q]);
                 const float t = wk * df[q] + dza * wa4[q];
                 d[q] = z[k][q] > 0.f ? t : t * 0.01f;
                 am = fmaxf(am, fabsf(d[q]));

@@ -2,8 +2,8 @@
 //
 // x = hi + lo with hi = fp16(x), lo = fp16(x - hi); a product w x is then carried as
 // w_hi x_hi + w_hi x_lo + w_lo x_hi in fp32 MFMA accumulators (22 significant bits per factor,
-// the dropped w_lo x_lo term <= 2^-22 |w x|).  Also the accurate sin / cos of the positional
-// encodings (networks.py:175-192 uses torch.sin / torch.cos in fp32).
+// the dropped w_lo x_lo term <= 2^-22 |w x|).  Also the one-instruction LeakyReLU and the accurate
+// sin / cos of the positional encodings (networks.py:175-192 uses torch.sin / torch.cos in fp32).
 #pragma once
 #include "agg_device.h"
 
@@ -57,6 +57,17 @@ __device__ __forceinline__ X3Pair split8_unit(const float (&v)[8]) {
     return r;
 }
 
+// LeakyReLU(0.01) exactly as the reference (x, or fp32(0.01 x) below zero): max(x, 0.01 x) as one
+// v_max_f32 in inline asm -- fmaxf on an MFMA result or a loaded value makes the compiler canonicalise
+// the operand with an extra v_max_f32 x, x, x first (IEEE mode); NaN / inf still propagate (the
+// fp16-range guard).  The asm writes into the register of 0.01 x ("+v", tied; see split8_unit for why).
+// Not agg_device.h's lrelu_max: that one is the f16 path's fma formula, within 1 ulp of this value.
+__device__ __forceinline__ float lrelu_x3(float a) {
+    float r = 0.01f * a;
+    asm("v_max_f32 %0, %1, %0" : "+v"(r) : "v"(a));
+    return r;
+}
+
 // sin and cos of x (fp32, within ~1 ulp): quadrant q = rint(x 2/pi), r = x - q pi/2 in double
 // (exact to far below fp32 resolution for |x| < 2^20), cephes' minimax polynomials on
 // [-pi/4, pi/4]; |x| >= 2^20 (never met by the encodings' arguments) takes the library sincosf.
@@ -79,6 +90,11 @@ __device__ __forceinline__ void sincos_acc(float x, float &s, float &c) {
         return;
     }
     sincos_acc_fast(x, s, c);
+}
+// sin / cos of x 2^F (the scaling is exact; torch.sin on the product, networks.py:186)
+template <int F>
+__device__ __forceinline__ void sincos_f(float x, float &s, float &c) {
+    sincos_acc(x * (float)(1 << F), s, c);
 }
 
 }  // namespace

@@ -76,6 +76,20 @@ def test_sizing_functions():
     assert L.sgn_aggregate_workspace_bytes(10_000) >= 10_000 * 256 * 2
 
 
+@pytest.mark.parametrize("S", [0, 31, 32, 33, 1000])
+def test_f32_aggregate_workspace_layout(S):
+    """The fp32 aggregator's workspace: per item 1 KiB of f_s, a 32-B row table and a 16-B slot entry,
+    then a 2-KiB tail whose second word is the fp16-range flag; at least 32 items."""
+    L = _lib.lib()
+    per, tail = 256 * 4 + 32 + 16, 2048
+    exact = L.sgn_aggregate_workspace_bytes_f32(S)
+    assert exact == max(S, 32) * per + tail
+    for b in (exact, exact - 1):
+        items = (b - tail) // per
+        assert L.sgn_aggregate_flag_offset_f32(b) == items * per + 4
+        assert L.sgn_aggregate_fs_offset_f32(b, S) == (0 if items >= max(S, 32) else -1)
+
+
 def test_argument_errors_are_reported_without_gpu():
     """Parameter validation runs before any HIP call: bad arguments give rc < 0 and a message."""
     L = _lib.lib()
