@@ -27,6 +27,8 @@
  *   sgn_composite    <- NeuralPointsRayMarching.forward ray_dist + ray_march + fill_invalid
  *                       models/neural_points_volumetric_model.py:569-631, :158-195
  *                       models/rendering/diff_ray_marching.py:509-555
+ *   sgn_probe        <- NeuralPointsRayMarching.forward, the opt.prob = 1 outputs + unmask
+ *                       models/neural_points_volumetric_model.py:633-668, :192-203
  */
 #ifndef SGN_HIP_H
 #define SGN_HIP_H
@@ -41,7 +43,7 @@ extern "C" {
 typedef void *sgn_stream_t; /* hipStream_t (torch.cuda.current_stream().cuda_stream) */
 typedef struct sgn_grid sgn_grid; /* opaque, device-resident voxel grid of one point cloud */
 
-#define SGN_ABI_VERSION 21
+#define SGN_ABI_VERSION 22
 
 /* ---- grid ------------------------------------------------------------- */
 
@@ -71,6 +73,12 @@ int sgn_grid_build(const float *d_points, int64_t n_points, const sgn_grid_param
                    sgn_stream_t stream, sgn_grid **out_grid);
 int sgn_grid_free(sgn_grid *grid);
 int sgn_grid_get_info(const sgn_grid *grid, sgn_grid_info *out);
+/* Changes query_size on a built grid (asynchronous, two passes over the voxel words): only the
+ * occupancy flags depend on it, so the slots and point lists are kept and the flags are drawn again;
+ * the grid then equals one built with that query_size.  For callers that switch it between frames
+ * (probe_hole's prob_kernel_size, run/train_ft.py:425-538) without rebuilding. */
+int sgn_grid_set_query_size(sgn_grid *grid, const int32_t *query, sgn_stream_t stream);
+
 /* Writes the reference's own grid structures (for parity tests):
  * coor_occ/coor_2_occ int32[volume], occ_numpnts int32[max_o], occ_2_pnts int32[max_o*P]. */
 int sgn_grid_export(const sgn_grid *grid, int32_t *d_coor_occ, int32_t *d_coor_2_occ,
@@ -650,6 +658,34 @@ int sgn_composite(const sgn_composite_params *cp, const float *d_campos, const f
 int sgn_ray_march_dense(const float *d_ray_dist, const uint8_t *d_valid, const float *d_feat, int64_t R,
                         int32_t SR, const float *bg, float *d_rgb, float *d_opacity, float *d_acc_t,
                         float *d_blendw, float *d_bgT, sgn_stream_t stream);
+
+/* ---- hole-probing maps (opt.prob = 1) --------------------------------------
+ * The per-ray maps run/train_ft.py's probe_hole reads from model.test() (reference
+ * neural_points_volumetric_model.py:633-668, expanded by unmask, :192-203), from one frame's query output
+ * (ray_ns, ray_soff, samp_locw, pidx), the point tables (xyz, embedding, color, dir, conf, n_points >= 1),
+ * d_opacity float[R*SR] (sgn_composite's out_opacity), d_blend float[S*K] (the aggregator's out_blend:
+ * normalised weight * clamped conf) and d_mask int8[R] (sgn_composite's out_mask).  K = 1 .. 8.
+ * d_out: one packed record of SGN_PROBE_RECORD floats per ray,
+ *   [0] opacity  [1] far_dist  [2] avg_conf  [3] 0 | [4..6] loc_w, [7] 0 | [8..10] avg_color, [11] 0 |
+ *   [12..14] avg_dir, [15] 0 | [16..47] avg_embedding
+ * For a ray with mask != 0:
+ *   j        = the first slot holding the maximum of d_opacity[r, 0 .. SR) (numpy.argmax's choice; the
+ *              reference's CUDA torch.max leaves the index among tied slots unspecified); j < ray_ns[r] on a
+ *              composite's output (slot 0 is a selected sample, every positive opacity belongs to one),
+ *              and the sample is s = ray_soff[r] + j
+ *   opacity  = d_opacity[r, j], loc_w = samp_locw[s]  (copies)
+ *   far_dist = min over all K slots k of || xyz[max(pidx[s K + k], 0)] - loc_w ||  (fp32 subtract, squares,
+ *              sum, sqrt): an empty slot (-1) reads point 0, as the reference's clamp before the gather does
+ *              (neural_points.py:958-959), so point 0's distance takes part whenever the sample has fewer
+ *              than K neighbours
+ *   avg_X    = sum over k (ascending, fp32) of blend[s K + k] * X[max(pidx[s K + k], 0)] for X = color, dir,
+ *              conf (raw) and the 32 embedding channels; an empty slot carries blend 0 (its d_blend entry
+ *              is not read)
+ * A ray with mask == 0 (or without a sample) gets an all-zero record.  d_out and the embedding table 16-B
+ * aligned.  R == 0 returns 0 without a launch. */
+#define SGN_PROBE_RECORD 48
+int sgn_probe(const sgn_point_tables *pt, const sgn_query_out *q, const float *d_opacity, const float *d_blend,
+              const int8_t *d_mask, int64_t R, int32_t SR, int32_t K, float *d_out, sgn_stream_t stream);
 
 /* ---- training loss stage (forward + backward) ----------------------------
  * Replaces the torch autograd of ray_dist + ray_march + fill_invalid and the training losses:

@@ -12,8 +12,9 @@ import torch  # noqa: F401  -- loads torch's libamdhip64 first so the .so binds 
 
 # SGN_HIP_LIB: another build of the same ABI (same-box A/B of kernel variants, tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SGN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsgn_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 COLSUM_SLABS = 512   # SGN_COLSUM_SLABS
+PROBE_RECORD = 48    # SGN_PROBE_RECORD
 
 c_i32, c_i64, c_u64, c_f32, c_vp, c_sz = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
                                          ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t)
@@ -102,6 +103,7 @@ SIGNATURES = {
     "sgn_grid_build": (c_i32, [c_vp, c_i64, ctypes.POINTER(GridParams), c_vp, ctypes.POINTER(c_vp)]),
     "sgn_grid_free": (c_i32, [c_vp]),
     "sgn_grid_get_info": (c_i32, [c_vp, ctypes.POINTER(GridInfo)]),
+    "sgn_grid_set_query_size": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_vp]),
     "sgn_grid_export": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgn_depth_table_jitter": (c_i32, [c_f32, c_f32, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp]),
     "sgn_query_workspace_bytes": (c_sz, [c_i64]),
@@ -196,6 +198,8 @@ SIGNATURES = {
     "sgn_mlp_pack_index_f32": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_i64]),
     "sgn_composite": (c_i32, [ctypes.POINTER(CompositeParams), c_vp, c_vp, c_vp, c_i64, c_vp, c_i32,
                               c_i32, ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgn_probe": (c_i32, [ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_i64, c_i32, c_i32,
+                          c_vp, c_vp]),
     "sgn_loss_workspace_bytes": (c_sz, [c_i64, c_i32]),
     "sgn_loss_train": (c_i32, [ctypes.POINTER(LossParams), c_vp, c_vp, c_i64, ctypes.POINTER(QueryOut), c_vp, c_vp,
                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

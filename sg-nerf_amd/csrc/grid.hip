@@ -132,6 +132,32 @@ __global__ void k_flag(const int32_t *__restrict__ slot_vox, int64_t n_slots, Gr
     }
 }
 
+// sgn_grid_set_query_size: the flags again, for another query_size, on a built grid.  Only the flagged-empty
+// words depend on query_size (the slots, the lists and the geometry do not), so they are cleared and
+// k_flag's neighbourhoods are drawn again from the mapped voxels themselves (vox >= 0 are exactly
+// slot_vox's entries): the same words a build with that query_size writes.
+__global__ void k_unflag(int64_t vol, int32_t *__restrict__ vox) {
+    for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < vol; v += (int64_t)gridDim.x * blockDim.x)
+        if (vox[v] == VOX_FLAGGED) vox[v] = VOX_UNFLAGGED;
+}
+
+__global__ void k_reflag(int64_t vol, GridGeom g, int3 qs, int32_t *__restrict__ vox) {
+    const int64_t plane = (int64_t)g.dy * g.dz;
+    for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < vol; v += (int64_t)gridDim.x * blockDim.x) {
+        if (vox[v] < 0) continue;   // slot words are never rewritten, so this test does not race with the flags
+        int cx = (int)(v / plane), cy = (int)((v / g.dz) % g.dy), cz = (int)(v % g.dz);
+        int x0 = max(0, cx - qs.x / 2), x1 = min(g.dx, cx + (qs.x + 1) / 2);
+        int y0 = max(0, cy - qs.y / 2), y1 = min(g.dy, cy + (qs.y + 1) / 2);
+        int z0 = max(0, cz - qs.z / 2), z1 = min(g.dz, cz + (qs.z + 1) / 2);
+        for (int x = x0; x < x1; ++x)
+            for (int y = y0; y < y1; ++y)
+                for (int z = z0; z < z1; ++z) {
+                    int32_t *c = vox + g.lin(x, y, z);
+                    if (*c == VOX_UNFLAGGED) *c = VOX_FLAGGED;  // benign: all writers store -1
+                }
+    }
+}
+
 // fill_occ2pnts routing (:394-396): slot of the point's voxel, the `> 0` bug
 // unless fix_occ0.  Unrouted points get the sentinel n_slots (sorted last).
 __global__ void k_point_slot(const int32_t *__restrict__ key, const int32_t *__restrict__ vox,
@@ -393,6 +419,21 @@ int sgn_grid_free(sgn_grid *g) {
     (void)hipFree(g->cell_pts);
     (void)hipFree(g->occ_sc);
     delete g;
+    return 0;
+}
+
+int sgn_grid_set_query_size(sgn_grid *g, const int32_t *query, sgn_stream_t stream) {
+    SGN_REQUIRE(g && query, "null grid/query");
+    SGN_REQUIRE(query[0] > 0 && query[1] > 0 && query[2] > 0, "query_size must be positive");
+    if (query[0] == g->p.query[0] && query[1] == g->p.query[1] && query[2] == g->p.query[2]) return 0;
+    hipStream_t st = sgn::as_stream(stream);
+    sgn::GridGeom geo{g->p.shift[0], g->p.shift[1], g->p.shift[2], g->p.vs[0], g->p.vs[1], g->p.vs[2],
+                      g->p.dims[0], g->p.dims[1], g->p.dims[2]};
+    hipLaunchKernelGGL(sgn::k_unflag, dim3(sgn::blocks_for(g->vol)), dim3(sgn::TPB), 0, st, g->vol, g->vox);
+    hipLaunchKernelGGL(sgn::k_reflag, dim3(sgn::blocks_for(g->vol)), dim3(sgn::TPB), 0, st, g->vol, geo,
+                       make_int3(query[0], query[1], query[2]), g->vox);
+    SGN_CHECK_HIP(hipGetLastError());
+    for (int a = 0; a < 3; ++a) g->p.query[a] = query[a];
     return 0;
 }
 

@@ -259,7 +259,17 @@ class HipPointsVolumetricModel:
         if self.net_ray_marching is None:
             raise RuntimeError("no neural points / weights: call load_networks() or set_points() first")
         self._sync_weights()
-        self.output = self.net_ray_marching.render(self.input)  # == fill_invalid(forward(input))
+        # opt.prob / opt.query_size are read on every call: probe_hole (run/train_ft.py:425-538) sets
+        # prob = 1 and query_size = prob_kernel_size on the live Namespace around its test() calls
+        prob = int(getattr(self.opt, "prob", 0) or 0)
+        qs = getattr(self.opt, "query_size", None)
+        if qs is not None:
+            qs = tuple(int(x) for x in np.asarray(qs).reshape(-1))
+            if len(qs) != 3 or qs[0] == 0:   # 0: "as kernel_size" (neural_points.py:425), resolved in self.opts
+                qs = None
+        if qs == tuple(self.opts.query_size):
+            qs = None
+        self.output = self.net_ray_marching.render(self.input, prob=prob, query_size=qs)  # == fill_invalid(forward(input))
         for k in self.visual_names:
             setattr(self, k, self.output[k])
 

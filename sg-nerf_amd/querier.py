@@ -61,6 +61,19 @@ class HipGrid:
                        "sgn_grid_build")
         self.n_points = pts.shape[0]
         self._keep = pts  # points must outlive nothing (grid holds its own copy); kept for checks
+        self.query_size = tuple(int(x) for x in opts.query_size)
+
+    def set_query_size(self, query_size):
+        """The occupancy flags for another query_size, on this grid (sgn_grid_set_query_size: the slots
+        and point lists do not depend on it and are kept).  No launch when it is the current one."""
+        qs = tuple(int(x) for x in query_size)
+        if len(qs) != 3:
+            raise ValueError(f"query_size takes three extents, got {query_size!r}")
+        if qs != self.query_size:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().sgn_grid_set_query_size(self.handle, (ctypes.c_int32 * 3)(*qs),
+                                                              _lib.stream_handle()), "sgn_grid_set_query_size")
+            self.query_size = qs
 
     def info(self):
         inf = _lib.GridInfo()
@@ -208,8 +221,11 @@ class LightningFastQuerier:
 
     # -- sample-major fast path ------------------------------------------------------
     def query_samples(self, point_xyz_w_tensor, campos, raydir, near, far, point_labels=None,
-                      ray_labels=None, seconds=None, count_traffic=False):
+                      ray_labels=None, seconds=None, count_traffic=False, query_size=None):
+        """`query_size`: overrides opts.query_size for this call (the cached grid is kept: only its
+        occupancy flags are drawn again, and the next call without the override draws them back)."""
         grid = self.grid_for(point_xyz_w_tensor)
+        grid.set_query_size(self.opts.query_size if query_size is None else query_size)
         R = raydir.shape[0]
         t, per_ray = self.depth_table(near, far, R)
         return run_query(grid, self.opts, campos.reshape(3).contiguous(), raydir.reshape(-1, 3).contiguous(),
@@ -228,6 +244,7 @@ class LightningFastQuerier:
         near_depth, far_depth = np.asarray(near_depth).item(), np.asarray(far_depth).item()
         pts_w = point_xyz_w_tensor.reshape(-1, 3)
         grid = self.grid_for(pts_w)
+        grid.set_query_size(o.query_size)
         raydir = ray_dirs_tensor.reshape(-1, 3).contiguous()
         R = raydir.shape[0]
         t, per_ray = self.depth_table(near_depth, far_depth, R)

@@ -142,6 +142,23 @@ class NeuralPoints:
 
 
 # ----------------------------------------------------------------------------------
+# The opt.prob = 1 outputs (neural_points_volumetric_model.py:633-668) and where each sits in sgn_probe's
+# packed per-ray record (include/sgn_hip.h): name -> (first float, channels); ray_max_sample_label is
+# zeros_like(shading_avg_conf) (:656).
+PROBE_FIELDS = {"ray_max_shading_opacity": (0, 1), "ray_max_far_dist": (1, 1), "shading_avg_conf": (2, 1),
+                "ray_max_sample_loc_w": (4, 3), "shading_avg_color": (8, 3), "shading_avg_dir": (12, 3),
+                "shading_avg_embedding": (16, 32)}
+PROBE_KEYS = ("ray_max_shading_opacity", "ray_max_sample_loc_w", "ray_max_sample_label", "ray_max_far_dist",
+              "shading_avg_color", "shading_avg_dir", "shading_avg_conf", "shading_avg_embedding")
+
+
+def _probe_maps(rec):
+    """[R', 48] packed records -> the eight [1, R', C] maps (fresh tensors)."""
+    out = {k: rec[None, :, o:o + c].clone() for k, (o, c) in PROBE_FIELDS.items()}
+    out["ray_max_sample_label"] = torch.zeros_like(out["shading_avg_conf"])
+    return {k: out[k] for k in PROBE_KEYS}
+
+
 def fill_invalid(output, input, bg_color=None):
     """neural_points_volumetric_model.py:158-195: expand the compacted [1,R'',.] outputs
     of forward() to all R rays (bg colour, background 1, opacity 0, queried_shading 1)."""
@@ -167,6 +184,12 @@ def fill_invalid(output, input, bg_color=None):
     fq = torch.ones(B, OR, qs.shape[2], dtype=qs.dtype, device=dev)
     fq[0, keep] = qs[0]
     output["queried_shading"] = fq
+    if "ray_max_shading_opacity" in output:   # the opt.prob = 1 maps: unmask, zeros (:192-203)
+        for name in PROBE_KEYS:
+            t = output[name]
+            full = torch.zeros((B, OR) + tuple(t.shape[2:]), dtype=t.dtype, device=dev)
+            full[0, keep] = t[0]
+            output[name] = full
     return output
 
 
@@ -192,7 +215,12 @@ class NeuralPointsRayMarching:
     coarse_point_opacity, queried_shading, coarse_is_background, ray_mask and, with
     `return_weights`, weight / blend_weight / conf_coefficient).  render(inputs) is the
     production entry: the same values already expanded by fill_invalid, without the
-    compaction round trip and without any host synchronisation."""
+    compaction round trip and without any host synchronisation.
+
+    Hole probing (opt.prob = 1, :633-668): with `prob=1` (or, left None, `opt.prob` read at call time
+    when the module was built from the driver's Namespace) both also return PROBE_KEYS, the per-ray
+    maps run/train_ft.py's probe_hole reads; `query_size` overrides opts.query_size for that call
+    (probe_hole's prob_kernel_size).  With the switch off nothing changes: no key, no launch."""
 
     def __init__(self, neural_points: NeuralPoints, aggregator_state, opt=None, device="cuda",
                  return_weights=True):
@@ -207,7 +235,12 @@ class NeuralPointsRayMarching:
     def set_aggregator_state(self, state):
         self.renderer.set_mlp(strip_prefix(state))
 
-    def _render(self, inputs, want_weights):
+    def _prob(self, prob):
+        if prob is None:
+            prob = 0 if isinstance(self.opt, HotPathOpts) or self.opt is None else getattr(self.opt, "prob", 0)
+        return int(prob or 0) == 1
+
+    def _render(self, inputs, want_weights, want_probe=False, query_size=None):
         self.renderer.points = self.neural_points.tables()
         campos = inputs["campos"].reshape(3)
         rot = inputs["camrotc2w"].reshape(3, 3)
@@ -225,7 +258,8 @@ class NeuralPointsRayMarching:
             rl = torch.as_tensor(inputs["pixel_label"]).reshape(-1).to(self.device, torch.int32).contiguous()
         return self.renderer.render(campos, rot, raydir, near, far, want_opacity=True, want_blend=False,
                                     bg=bg, want_weights=want_weights, point_labels=pl, ray_labels=rl,
-                                    seconds=inputs.get("seconds")), raydir.shape[0]
+                                    seconds=inputs.get("seconds"), want_probe=want_probe,
+                                    query_size=query_size), raydir.shape[0]
 
     def _weights(self, out, R):
         """weight [R,SR,K], blend_weight [R,SR,1], conf_coefficient [R,SR,K] (dense ray slots)."""
@@ -238,10 +272,11 @@ class NeuralPointsRayMarching:
         conf_coef = torch.clamp(conf[torch.clamp(pidx, min=0).long()], 1e-4, 1.0)
         return weight, out.blendw[:R, :, None], conf_coef
 
-    def render(self, inputs):
+    def render(self, inputs, prob=None, query_size=None):
         """Expanded outputs (what fill_invalid(forward(inputs)) gives), no host sync.
         Fresh tensors, as the reference returns (the renderer's buffers are reused)."""
-        out, R = self._render(inputs, self.return_weights)
+        want_probe = self._prob(prob)
+        out, R = self._render(inputs, self.return_weights, want_probe, query_size)
         rgb = out.rgb[None].clone()
         if inputs.get("bg_ray") is not None:   # T_bg * bg_ray + colour (neural_points_volumetric_model.py:114-116)
             bg_ray = torch.as_tensor(inputs["bg_ray"]).to(self.device, torch.float32).reshape(1, R, 3)
@@ -257,11 +292,14 @@ class NeuralPointsRayMarching:
         if self.return_weights:
             w, bw, cc = self._weights(out, R)
             res["weight"], res["blend_weight"], res["conf_coefficient"] = w[None], bw[None].clone(), cc[None]
+        if want_probe:   # sgn_probe wrote zero records for the rays outside the mask (unmask, :192-203)
+            res.update(_probe_maps(out.probe))
         return res
 
-    def forward(self, inputs, **kargs):
+    def forward(self, inputs, prob=None, query_size=None, **kargs):
         """Reference forward: compacted [1,R'',...] outputs + ray_mask [1,R]."""
-        out, R = self._render(inputs, self.return_weights)
+        want_probe = self._prob(prob)
+        out, R = self._render(inputs, self.return_weights, want_probe, query_size)
         keep = torch.nonzero(out.ray_mask).reshape(-1)
         res = {
             "coarse_raycolor": out.rgb[keep][None],
@@ -273,6 +311,8 @@ class NeuralPointsRayMarching:
         if self.return_weights:
             w, bw, cc = self._weights(out, R)
             res["weight"], res["blend_weight"], res["conf_coefficient"] = w[keep][None], bw[keep][None], cc[keep][None]
+        if want_probe:
+            res.update(_probe_maps(out.probe[keep]))
         return res
 
     __call__ = forward

@@ -26,6 +26,7 @@ class RenderOut:
     blend: torch.Tensor      # [S_cap,8] weight * conf_coefficient (when want_blend)
     wnorm: torch.Tensor = None    # [S_cap,8] normalised weight (when want_weights)
     blendw: torch.Tensor = None   # [R,SR] alpha-blend weight o*T (when want_weights)
+    probe: torch.Tensor = None    # [R,48] packed hole-probing records (sgn_probe; when want_probe)
 
 
 class PointTables:
@@ -106,6 +107,7 @@ class HipRenderer:
             self.opacity = torch.empty(max(R, 1), SR, dtype=torch.float32, device=dev)
             self.wnorm = None
             self.blendw = None
+            self.probe = None
             self._cap = (R, cap)
 
     def _flag(self):
@@ -157,7 +159,7 @@ class HipRenderer:
 
     def render(self, campos, camrotc2w, raydir, near, far, want_opacity=True, want_blend=False, marks=None,
                bg=None, want_weights=False, point_labels=None, ray_labels=None, seconds=None,
-               count_traffic=False, check_range="sync"):
+               count_traffic=False, check_range="sync", want_probe=False, query_size=None):
         """One frame.  `marks(name)` (optional) is called between stages on the host thread
         (bench.py records HIP events on the current stream there).  `bg`: 3 floats
         overriding opts.bg_color.  `want_weights`: also produce the normalised neighbour
@@ -165,8 +167,13 @@ class HipRenderer:
         `point_labels` [N] / `ray_labels` [R] int32 (+ `seconds`): the SG semantic-guided kNN
         (semantic_guidance = 1, worldcoords.py:839-938).  `check_range`: the f32 mode's fp16-range
         guard ("sync" default: a frame whose activations leave fp16 range is re-rendered on the
-        plain-fp32 path, sgn_aggregate_exact; "deferred" for pipelined frame loops + finish(), False)."""
+        plain-fp32 path, sgn_aggregate_exact; "deferred" for pipelined frame loops + finish(), False).
+        `want_probe`: also the per-ray hole-probing records (opt.prob = 1; sgn_probe, RenderOut.probe
+        [R, 48]); implies want_opacity and want_blend.  `query_size`: overrides opts.query_size for this
+        call (probe_hole's prob_kernel_size); the cached grid is kept."""
         o = self.opts
+        if want_probe:
+            want_opacity = want_blend = True
         mark = marks or (lambda name: None)
         campos = campos.reshape(3).to(self.device, torch.float32).contiguous()
         rot = camrotc2w.reshape(3, 3).to(self.device, torch.float32).contiguous()
@@ -178,11 +185,13 @@ class HipRenderer:
             self.blendw = torch.empty(max(self._cap[0], 1), o.SR, dtype=torch.float32, device=self.device)
         if want_weights:
             self.wnorm.zero_()
+        if want_probe and self.probe is None:
+            self.probe = torch.empty(max(self._cap[0], 1), _lib.PROBE_RECORD, dtype=torch.float32, device=self.device)
         mark("query")
         if o.semantic_guidance == 1 and (point_labels is None or ray_labels is None):
             raise ValueError("semantic_guidance = 1 needs point_labels and ray_labels")
         q = self.querier.query_samples(self.points.xyz, campos, raydir, near, far, point_labels, ray_labels, seconds,
-                                       count_traffic)
+                                       count_traffic, query_size)
         L = _lib.lib()
         st = _lib.stream_handle()
         pt = _lib.PointTables()
@@ -253,11 +262,22 @@ class HipRenderer:
                                        _lib.ptr(self.opacity) if want_opacity else None,
                                        _lib.ptr(self.blendw) if want_weights else None, _lib.stream_handle()),
                        "sgn_composite")
+
+        def probe():
+            # after the composite: reads its opacity and mask, and the aggregator's blend
+            if want_probe:
+                _lib.check(L.sgn_probe(ctypes.byref(pt), ctypes.byref(qo), _lib.ptr(self.opacity), _lib.ptr(self.blend),
+                                       _lib.ptr(self.mask), R, o.SR, o.K, _lib.ptr(self.probe), _lib.stream_handle()),
+                           "sgn_probe")
         composite()
+        if want_probe:
+            mark("probe")
+            probe()
         mark("end")
-        self._range_check(check_range, lambda: (aggregate_exact(), composite()))
+        self._range_check(check_range, lambda: (aggregate_exact(), composite(), probe()))
         return RenderOut(self.rgb[:R], self.mask[:R], self.bgT[:R], self.opacity[:R], q, self.feat, self.blend,
-                         self.wnorm if want_weights else None, self.blendw[:R] if want_weights else None)
+                         self.wnorm if want_weights else None, self.blendw[:R] if want_weights else None,
+                         self.probe[:R] if want_probe else None)
 
     def points_projected(self):
         """The last frame's projected point count and the neighbour indices >= n_points met so far
