@@ -43,7 +43,7 @@ extern "C" {
 typedef void *sgn_stream_t; /* hipStream_t (torch.cuda.current_stream().cuda_stream) */
 typedef struct sgn_grid sgn_grid; /* opaque, device-resident voxel grid of one point cloud */
 
-#define SGN_ABI_VERSION 22
+#define SGN_ABI_VERSION 23
 
 /* ---- grid ------------------------------------------------------------- */
 
@@ -169,7 +169,28 @@ typedef struct {
      * camrotc2w must still be valid pointers (unused values when pers is given). */
     const float *pers;       /* [N,3] or NULL */
     const float *samp_pers;  /* [S,3] or NULL (with pers) */
+    /* rotated neural points (ABI 23; NULL = unrotated, the behaviour of every earlier ABI): the
+     * reference's per-point Rw2c (neural_points.py:967, viewmlp point_aggregators.py:565-569, :579,
+     * :599, :648).  With R_p the point's matrix and y = R x meaning y_i = sum_j R[i][j] x_j:
+     *   the world half of dists becomes R_p (xyz_p - loc_s) before its encoding (the weights keep the
+     *   unrotated offset; the pers half is not rotated);
+     *   the view direction of a sample is R_{p0(s)} raydir, p0(s) the point in its neighbour slot 0,
+     *   everywhere downstream (block3.0's extras and the colour MLP's PE);
+     *   the point direction in block3.0's extras is R_p dir_p.
+     * Honoured by sgn_aggregate, sgn_aggregate_f32 and sgn_aggregate_exact for the base network
+     * (bpnet_layers = 0) without pers; sgn_point_project[_f32] accept it (P and the point record do
+     * not depend on it); sgn_probe ignores it; every other entry taking this struct returns an
+     * argument error naming rot. */
+    const float *rot;          /* [N,9] row-major Rw2c per point, or NULL */
+    const float *samp_viewdir; /* [S,3] rotated view direction per sample id (sgn_sample_viewdirs);
+                                  required with rot */
 } sgn_point_tables;
+
+/* Rotated neural points: d_out[s] = rot[pidx[s*K]] raydir[samp_ray[s]] for every work-list sample s
+ * (float[S_capacity*3]; samples outside the work list are left as they are).  pt->rot, pt->raydir,
+ * pt->n_points and q's counters / work / samp_ray / pidx are read. */
+int sgn_sample_viewdirs(const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
+                        float *d_out, sgn_stream_t stream);
 
 /* The packed fp16 weight blob (MFMA fragment-major): its size, and the pack from host weights to a
  * device blob (synchronous copy).  sgn_mlp_section: byte offsets inside it, 0 = fp32 section,

@@ -12,7 +12,7 @@ import torch  # noqa: F401  -- loads torch's libamdhip64 first so the .so binds 
 
 # SGN_HIP_LIB: another build of the same ABI (same-box A/B of kernel variants, tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SGN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsgn_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 COLSUM_SLABS = 512   # SGN_COLSUM_SLABS
 PROBE_RECORD = 48    # SGN_PROBE_RECORD
 
@@ -46,7 +46,7 @@ class QueryOut(ctypes.Structure):
 class PointTables(ctypes.Structure):
     _fields_ = [("xyz", c_vp), ("embedding", c_vp), ("color", c_vp), ("dir", c_vp),
                 ("conf", c_vp), ("n_points", c_i64), ("campos", c_vp), ("camrotc2w", c_vp),
-                ("raydir", c_vp), ("pers", c_vp), ("samp_pers", c_vp)]
+                ("raydir", c_vp), ("pers", c_vp), ("samp_pers", c_vp), ("rot", c_vp), ("samp_viewdir", c_vp)]
 
 
 class AggSaved(ctypes.Structure):
@@ -115,6 +115,7 @@ SIGNATURES = {
     "sgn_aggregate": (c_i32, [c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64,
                               c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_i32, c_vp]),
     "sgn_bpnet_pack": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "sgn_sample_viewdirs": (c_i32, [ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_i64, c_i32, c_vp, c_vp]),
     "sgn_point_proj_bytes": (c_sz, [c_i64]),
     "sgn_point_project": (c_i32, [ctypes.POINTER(PointTables), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgn_mlp_section": (c_sz, [c_i32]),

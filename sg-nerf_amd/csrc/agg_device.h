@@ -122,7 +122,17 @@ struct AggArgs {
     // neighbours per sample of the query's pidx (1..8): a sample's row k < K reads pidx index s * K + k,
     // rows k >= K are empty (fp32 kernels: a row-table entry s * 8 + k names pidx index s * K + k)
     int32_t K;
+    // rotated neural points (sgn_point_tables::rot / samp_viewdir; rotated instantiations only):
+    // prot [N,9] row-major Rw2c per point, samp_v [S,3] the sample's rotated view direction
+    const float *prot, *samp_v;
 };
+
+// y = R x, y_i = sum_j R[i][j] x_j (point_aggregators.py:565: x @ Rw2c^T), every op IEEE-rounded
+__device__ __forceinline__ void rot3(const float (&R)[9], float x, float y, float z, float &ox, float &oy, float &oz) {
+    ox = __fadd_rn(__fadd_rn(__fmul_rn(R[0], x), __fmul_rn(R[1], y)), __fmul_rn(R[2], z));
+    oy = __fadd_rn(__fadd_rn(__fmul_rn(R[3], x), __fmul_rn(R[4], y)), __fmul_rn(R[5], z));
+    oz = __fadd_rn(__fadd_rn(__fmul_rn(R[6], x), __fmul_rn(R[7], y)), __fmul_rn(R[8], z));
+}
 
 // host: the fields every entry point fills the same way (pers / samp_pers are the caller's business:
 // the training entries take none)
@@ -132,6 +142,7 @@ inline void fill_agg_args(AggArgs &a, const sgn_point_tables *pt, const sgn_quer
     a.counters = q->counters; a.work = q->work; a.samp_ray = q->samp_ray; a.pidx = q->pidx;
     a.samp_locw = q->samp_locw;
     a.K = K;
+    a.prot = pt->rot; a.samp_v = pt->samp_viewdir;
 }
 
 // training save: one 16-byte fragment of a 32-row tile -> [rows][C] (C multiple of 16)
@@ -286,7 +297,10 @@ __device__ __forceinline__ RowIdx row_index(const AggArgs &a, int item, int end,
 // FEAT = false: the point features are not needed (split block1.0).  Block3's extra channels
 // (colour, dir - v, <dir, v>, 0; lane-half 0 only, zero on half 1) go to `ext` as fp16 or, with
 // F32EXT, to `extf` in fp32 (the fp32-faithful kernels split them themselves).
-template <bool FEAT, bool F32EXT>
+// ROT (a.prot, a.samp_v): the point's Rw2c turns the world offset (after the weights, which keep the
+// unrotated one, neural_points.py:943-947) and the point direction; the view direction is the
+// sample's rotated one (point_aggregators.py:565-569, :599, :648).
+template <bool FEAT, bool F32EXT, bool ROT = false>
 __device__ __forceinline__ RowIn gather_row_impl(const AggArgs &a, const Cam &cam, const RowIdx &ix, int lane,
                                                  float (&feat)[16], float (&dist)[3], h8 &ext, float (&extf)[8]) {
     const int h = lane >> 5, kk = lane & 7;
@@ -300,8 +314,8 @@ __device__ __forceinline__ RowIn gather_row_impl(const AggArgs &a, const Cam &ca
     const float lx = a.samp_locw[(int64_t)s * 3 + 0], ly = a.samp_locw[(int64_t)s * 3 + 1],
                 lz = a.samp_locw[(int64_t)s * 3 + 2];
     const int ray = ix.ray;
-    const float vx = a.raydir[(int64_t)ray * 3 + 0], vy = a.raydir[(int64_t)ray * 3 + 1],
-                vz = a.raydir[(int64_t)ray * 3 + 2];
+    const float *vp = ROT ? a.samp_v + (int64_t)s * 3 : a.raydir + (int64_t)ray * 3;
+    const float vx = vp[0], vy = vp[1], vz = vp[2];
     float px = 0.f, py = 0.f, pz = 0.f, cf = 0.f;
     float col[3] = {0.f, 0.f, 0.f}, pdr[3] = {0.f, 0.f, 0.f};
     if (m) {
@@ -327,6 +341,15 @@ __device__ __forceinline__ RowIn gather_row_impl(const AggArgs &a, const Cam &ca
     // dists (point_aggregators.py:917-925): half 0 world offsets, half 1 pers-space terms
     const float dwx = __fsub_rn(px, lx), dwy = __fsub_rn(py, ly), dwz = __fsub_rn(pz, lz);
     dist[0] = m ? dwx : 0.f; dist[1] = m ? dwy : 0.f; dist[2] = m ? dwz : 0.f;
+    if constexpr (ROT) {
+        if (m) {
+            float R[9];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) R[c] = a.prot[(int64_t)pid * 9 + c];
+            rot3(R, pdr[0], pdr[1], pdr[2], pdr[0], pdr[1], pdr[2]);
+            rot3(R, dwx, dwy, dwz, dist[0], dist[1], dist[2]);
+        }
+    }
     if (h == 1) {
         float xp = 0.f, yp = 0.f, zp = 0.f, xl, yl, zl;
         if (a.pers) {
@@ -374,11 +397,11 @@ __device__ __forceinline__ RowIn gather_row_impl(const AggArgs &a, const Cam &ca
     return ri;
 }
 
-template <bool FEAT = true>
+template <bool FEAT = true, bool ROT = false>
 __device__ __forceinline__ RowIn gather_row(const AggArgs &a, const Cam &cam, const RowIdx &ix, int lane,
                                             float (&feat)[16], float (&dist)[3], h8 &ext) {
     float unused[8];
-    return gather_row_impl<FEAT, false>(a, cam, ix, lane, feat, dist, ext, unused);
+    return gather_row_impl<FEAT, false, ROT>(a, cam, ix, lane, feat, dist, ext, unused);
 }
 
 template <bool FEAT = true>

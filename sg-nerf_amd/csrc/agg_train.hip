@@ -602,6 +602,7 @@ int sgn_aggregate_backward(int32_t bpnet_layers, int32_t bpnet_dim, const sgn_po
     SGN_REQUIRE(n_items >= 0, "n_items < 0");
     SGN_REQUIRE(K >= 1 && K <= 8, "the MFMA aggregator takes K = 1 .. 8 neighbours per sample");
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir && !pt->pers, "camera required, no precomputed pers");
+    SGN_REQUIRE_NO_ROT(pt);
     if (n_items == 0) return 0;
     SGN_REQUIRE(d_dfs && d_dalpha && saved->h1 && saved->h2 && saved->h3, "null saved/input tensors");
     SGN_REQUIRE(deltas->d1 && deltas->d2 && deltas->d3 && deltas->d4 && deltas->h4 && deltas->dza, "null delta outputs");

@@ -131,7 +131,8 @@ struct XRow {
     float d[6], ext[8], wgt;
 };
 
-template <bool PERS>
+// ROT: rotated neural points (a.prot, a.samp_v; gather_row_impl states the three rules)
+template <bool PERS, bool ROT>
 __device__ __forceinline__ XRow x_row(const AggArgs &a, const Cam &cam, int item, int end, int k) {
     XRow x;
     x.sval = item < end;
@@ -141,8 +142,8 @@ __device__ __forceinline__ XRow x_row(const AggArgs &a, const Cam &cam, int item
     x.ray = x.sval ? a.samp_ray[x.s] : 0;
     const int64_t s = x.s, pid = x.m ? x.pid : 0;
     const float lx = a.samp_locw[s * 3], ly = a.samp_locw[s * 3 + 1], lz = a.samp_locw[s * 3 + 2];
-    const float vx = a.raydir[(int64_t)x.ray * 3], vy = a.raydir[(int64_t)x.ray * 3 + 1],
-                vz = a.raydir[(int64_t)x.ray * 3 + 2];
+    const float *vp = ROT ? a.samp_v + s * 3 : a.raydir + (int64_t)x.ray * 3;
+    const float vx = vp[0], vy = vp[1], vz = vp[2];
     const float px = a.xyz[pid * 3], py = a.xyz[pid * 3 + 1], pz = a.xyz[pid * 3 + 2];
     const float dwx = __fsub_rn(px, lx), dwy = __fsub_rn(py, ly), dwz = __fsub_rn(pz, lz);
     float xp, yp, zp, xl, yl, zl;
@@ -153,9 +154,20 @@ __device__ __forceinline__ XRow x_row(const AggArgs &a, const Cam &cam, int item
         cam.pers(px, py, pz, xp, yp, zp);
         cam.pers(lx, ly, lz, xl, yl, zl);
     }
-    x.d[0] = x.m ? dwx : 0.f;
-    x.d[1] = x.m ? dwy : 0.f;
-    x.d[2] = x.m ? dwz : 0.f;
+    float R[ROT ? 9 : 1];
+    if constexpr (ROT) {
+        float r0, r1, r2;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) R[c] = a.prot[pid * 9 + c];
+        rot3(R, dwx, dwy, dwz, r0, r1, r2);  // the weights below keep the unrotated offset
+        x.d[0] = x.m ? r0 : 0.f;
+        x.d[1] = x.m ? r1 : 0.f;
+        x.d[2] = x.m ? r2 : 0.f;
+    } else {
+        x.d[0] = x.m ? dwx : 0.f;
+        x.d[1] = x.m ? dwy : 0.f;
+        x.d[2] = x.m ? dwz : 0.f;
+    }
     x.d[3] = x.m ? __fsub_rn(__fmul_rn(xp, zp), __fmul_rn(xl, zl)) : 0.f;
     x.d[4] = x.m ? __fsub_rn(__fmul_rn(yp, zp), __fmul_rn(yl, zl)) : 0.f;
     x.d[5] = x.m ? __fsub_rn(zp, zl) : 0.f;
@@ -174,7 +186,8 @@ __device__ __forceinline__ XRow x_row(const AggArgs &a, const Cam &cam, int item
     }
     // block3's extra channels: colour, dir - v, <dir, v> (:639-652)
     const float c0 = a.color[pid * 3], c1 = a.color[pid * 3 + 1], c2 = a.color[pid * 3 + 2];
-    const float e0 = a.dir[pid * 3], e1 = a.dir[pid * 3 + 1], e2 = a.dir[pid * 3 + 2];
+    float e0 = a.dir[pid * 3], e1 = a.dir[pid * 3 + 1], e2 = a.dir[pid * 3 + 2];
+    if constexpr (ROT) rot3(R, e0, e1, e2, e0, e1, e2);
     x.ext[0] = x.m ? c0 : 0.f;
     x.ext[1] = x.m ? c1 : 0.f;
     x.ext[2] = x.m ? c2 : 0.f;
@@ -188,7 +201,7 @@ __device__ __forceinline__ XRow x_row(const AggArgs &a, const Cam &cam, int item
 
 // SG: KSG > 0 adds block2_bpnet.0 ([h | BPNet embedding of bpnet_dim] -> 256) between block1.2
 // and block3.0 (point_aggregators.py:345-354, :629-636)
-template <bool PERS, int NTB>
+template <bool PERS, int NTB, bool ROT = false>
 __global__ __launch_bounds__(TPB, 1) void k_rows_exact(XArgs xa) {
     __shared__ __attribute__((aligned(16))) float lds[KCH * LSTR];
     const AggArgs &a = xa.a;
@@ -204,7 +217,7 @@ __global__ __launch_bounds__(TPB, 1) void k_rows_exact(XArgs xa) {
         int g = lane >> 4;
         asm volatile("" : "+v"(g));
         const int item = a.item0 + tile * 2 * NW + 2 * w + (r >> 3);
-        const XRow x = x_row<PERS>(a, cam, item, end, k);
+        const XRow x = x_row<PERS, ROT>(a, cam, item, end, k);
         const int64_t pid = x.m ? x.pid : 0;
         const float *emb = a.emb + pid * 32;
         // block1.0: [feat 32 | PE(feat, 3) 192 | PE(dists, 5) 60] (networks.py:175-192: sin / cos
@@ -319,6 +332,7 @@ __global__ __launch_bounds__(TPB, 1) void k_rows_exact(XArgs xa) {
 
 // colour MLP (point_aggregators.py:779-786): [f_s | PE(viewdir, 4) sin 12 | cos 12] -> 128 -> 128
 // -> 128 -> 3, sigmoid * (1 + 2e-3) - 1e-3; 16 work items per wave, one per lane row
+template <bool ROT = false>
 __global__ __launch_bounds__(TPB, 1) void k_color_exact(XArgs xa) {
     __shared__ __attribute__((aligned(16))) float lds[KCH * LSTR];
     const AggArgs &a = xa.a;
@@ -332,7 +346,8 @@ __global__ __launch_bounds__(TPB, 1) void k_color_exact(XArgs xa) {
         const bool sval = item < end;
         const int s = sval ? a.work[item] : 0;
         const int ray = a.samp_ray[s];
-        const float v3[3] = {a.raydir[(int64_t)ray * 3], a.raydir[(int64_t)ray * 3 + 1], a.raydir[(int64_t)ray * 3 + 2]};
+        const float *vp = ROT ? a.samp_v + (int64_t)s * 3 : a.raydir + (int64_t)ray * 3;
+        const float v3[3] = {vp[0], vp[1], vp[2]};
         const float *fs = xa.fs + (int64_t)(sval ? item - a.item0 : 0) * HID;
         f32x4 c0[8], c1[8];
         bias_x(c0, xa.w + ly.l[LC0].b, g);
@@ -455,6 +470,7 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir, "camera (campos, camrotc2w, raydir) required");
     SGN_REQUIRE((pt->pers == nullptr) == (pt->samp_pers == nullptr), "pers and samp_pers go together");
     SGN_REQUIRE(S_capacity >= 0 && S_capacity < (1 << 30), "S_capacity out of range");
+    SGN_REQUIRE_ROT(pt, bpnet_layers);
     const int64_t ws_items = (int64_t)(workspace_bytes / (HID * 4));
     SGN_REQUIRE(ws_items >= 1, "exact aggregate workspace too small (1 KiB per work item of a chunk)");
     hipStream_t st = as_stream(stream);
@@ -478,7 +494,9 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
         a.n_items = (int32_t)(S_capacity - i0 < chunk ? S_capacity - i0 : chunk);
         const int64_t tr = (a.n_items + 2 * NW - 1) / (2 * NW), tc = (a.n_items + 16 * NW - 1) / (16 * NW);
         const dim3 gr((unsigned)(tr < 2048 ? tr : 2048)), gc((unsigned)(tc < 1024 ? tc : 1024));
-        if (pt->pers) {
+        if (pt->rot) {  // base network, no pers (SGN_REQUIRE_ROT)
+            hipLaunchKernelGGL((k_rows_exact<false, 0, true>), gr, dim3(TPB), 0, st, x);
+        } else if (pt->pers) {
             if (ntb == 0) hipLaunchKernelGGL((k_rows_exact<true, 0>), gr, dim3(TPB), 0, st, x);
             else if (ntb == 16) hipLaunchKernelGGL((k_rows_exact<true, 16>), gr, dim3(TPB), 0, st, x);
             else hipLaunchKernelGGL((k_rows_exact<true, 22>), gr, dim3(TPB), 0, st, x);
@@ -487,7 +505,7 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
             else if (ntb == 16) hipLaunchKernelGGL((k_rows_exact<false, 16>), gr, dim3(TPB), 0, st, x);
             else hipLaunchKernelGGL((k_rows_exact<false, 22>), gr, dim3(TPB), 0, st, x);
         }
-        hipLaunchKernelGGL(k_color_exact, gc, dim3(TPB), 0, st, x);
+        hipLaunchKernelGGL(pt->rot ? k_color_exact<true> : k_color_exact<false>, gc, dim3(TPB), 0, st, x);
     }
     SGN_CHECK_HIP(hipGetLastError());
     return 0;

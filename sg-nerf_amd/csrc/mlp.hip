@@ -288,7 +288,8 @@ __device__ __forceinline__ void chain_out(const f32x16 (&acc)[TP], h8 (&out)[16]
         }
 }
 
-template <int V, bool SAVE = false>
+// ROT: rotated neural points (per-point Rw2c, gather_row_impl)
+template <int V, bool SAVE = false, bool ROT = false>
 __global__ __launch_bounds__(ROWS_TPB, 1) void k_agg_rows(AggArgs a) {
     constexpr int KSB = vksb(V);
     constexpr bool SPLIT = vsplit(V);
@@ -362,7 +363,7 @@ __global__ __launch_bounds__(ROWS_TPB, 1) void k_agg_rows(AggArgs a) {
         const int item = base + w * 4 + q;
         float feat[16], dist[3];
         h8 ext;
-        const RowIn ri = gather_row<!SPLIT>(a, cam, nx, lane, feat, dist, ext);
+        const RowIn ri = gather_row<!SPLIT, ROT>(a, cam, nx, lane, feat, dist, ext);
         const int nitem = item + gridDim.x * WG_SAMPLES;
 
         const int64_t srow0 = (int64_t)(base + w * 4 - a.item0) * 8;  // first saved row of this wave (SAVE)
@@ -552,6 +553,7 @@ struct ColorArgs {
     const _Float16 *fs;
     float *feat;
     int32_t item0, n_items;
+    const float *viewdir;  // ROT: [S,3] the sample's rotated view direction (sgn_sample_viewdirs)
 };
 
 // Colour MLP, one 512-thread workgroup per CU: the 136 colour fragments (C0..C2, 136 KiB)
@@ -588,6 +590,7 @@ __device__ __forceinline__ void color_layer(const char *wl, const float *bl, con
     }
 }
 
+template <bool ROT = false>
 __global__ __launch_bounds__(COL_TPB, 1) void k_color(ColorArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[COL_LDS];
     const int lane = threadIdx.x & 63;
@@ -628,7 +631,8 @@ __global__ __launch_bounds__(COL_TPB, 1) void k_color(ColorArgs a) {
         for (int k = 0; k < 16; ++k) x[k] = row[2 * k + h];
         // PE(viewdir) ori=True, channels [3:] (point_aggregators.py:579-585, networks.py:175-192):
         // pe[d*4+f] = sin(v_d 2^f), pe[12+d*4+f] = cos(v_d 2^f)
-        const float v[3] = {a.raydir[(int64_t)ray * 3], a.raydir[(int64_t)ray * 3 + 1], a.raydir[(int64_t)ray * 3 + 2]};
+        const float *vp = ROT ? a.viewdir + (int64_t)s * 3 : a.raydir + (int64_t)ray * 3;
+        const float v[3] = {vp[0], vp[1], vp[2]};
         float pe[24];
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
@@ -777,6 +781,32 @@ __global__ __launch_bounds__(256) void k_to_f16(const float *__restrict__ src, _
         } else {
             for (int64_t k = i; k < n; ++k) dst[k] = (_Float16)src[k];
         }
+    }
+}
+
+// Rotated neural points: the view direction of every work-list sample, turned by the Rw2c of the
+// point in its neighbour slot 0 (point_aggregators.py:568, :579; a missing slot-0 neighbour reads
+// point 0, the reference's clamp at neural_points.py:958).  One thread per work item.
+__global__ __launch_bounds__(256) void k_sample_viewdirs(const int32_t *__restrict__ counters,
+                                                         const int32_t *__restrict__ work,
+                                                         const int32_t *__restrict__ samp_ray,
+                                                         const int32_t *__restrict__ pidx, const float *__restrict__ raydir,
+                                                         const float *__restrict__ prot, int64_t n_points, int64_t S,
+                                                         int32_t K, float *__restrict__ out) {
+    const int64_t end = min((int64_t)counters[1], S);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < end; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = work[i];
+        if (s < 0 || s >= S) continue;
+        const int64_t p = min(max((int64_t)pidx[s * K], (int64_t)0), n_points - 1);
+        const float *v = raydir + (int64_t)samp_ray[s] * 3;
+        float R[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) R[c] = prot[p * 9 + c];
+        float o[3];
+        rot3(R, v[0], v[1], v[2], o[0], o[1], o[2]);
+        out[s * 3] = o[0];
+        out[s * 3 + 1] = o[1];
+        out[s * 3 + 2] = o[2];
     }
 }
 
@@ -955,6 +985,7 @@ int sgn_aggregate(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f
     const uint8_t *P = (const uint8_t *)d_packed;
     SGN_REQUIRE((pt->pers == nullptr) == (pt->samp_pers == nullptr), "pers and samp_pers go together");
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir, "camera (campos, camrotc2w, raydir) required");
+    SGN_REQUIRE_ROT(pt, ksb);
     AggArgs a{};
     fill_agg_args(a, pt, q, K);
     a.pers = pt->pers; a.samp_pers = pt->samp_pers;
@@ -966,6 +997,7 @@ int sgn_aggregate(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f
     ColorArgs c;
     c.counters = q->counters; c.work = q->work; c.samp_ray = q->samp_ray; c.raydir = pt->raydir;
     c.blob = P; c.fs = a.fs; c.feat = d_out_feat;
+    c.viewdir = pt->samp_viewdir;
     for (int64_t i0 = 0; i0 < S_capacity; i0 += chunk) {
         int64_t n = S_capacity - i0 < chunk ? S_capacity - i0 : chunk;
         a.item0 = c.item0 = (int32_t)i0;
@@ -981,11 +1013,12 @@ int sgn_aggregate(int32_t bpnet_layers, int32_t bpnet_dim, const void *d_bpnet_f
                                                                                 : k_agg_rows<KB + SP>)
                                      : (ksb == 0 ? k_agg_rows<0> : ksb == KS_HID ? k_agg_rows<KS_HID>
                                                                                 : k_agg_rows<KB>);
+            if (pt->rot) kern = d_point_proj ? k_agg_rows<SP, false, true> : k_agg_rows<0, false, true>;  // base only
             hipLaunchKernelGGL(kern, g1, dim3(ROWS_TPB), 0, st, a);
         }
         int64_t wg2 = (n + 32 * (COL_TPB / 64) - 1) / (32 * (COL_TPB / 64));  // 32 samples per wave
         dim3 g2((unsigned)(wg2 < 256 ? wg2 : 256));  // persistent: colour weights loaded once per CU
-        if (stages & 2) hipLaunchKernelGGL(k_color, g2, dim3(COL_TPB), 0, st, c);
+        if (stages & 2) hipLaunchKernelGGL(pt->rot ? k_color<true> : k_color<false>, g2, dim3(COL_TPB), 0, st, c);
     }
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
@@ -1005,6 +1038,7 @@ int sgn_aggregate_train_fwd(int32_t bpnet_layers, int32_t bpnet_dim, const void 
                 "bpnet_dim > 0 needs the 16-byte aligned fp16 BPNet point embedding");
     SGN_REQUIRE(K >= 1 && K <= 8, "the MFMA aggregator takes K = 1 .. 8 neighbours per sample");
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir && !pt->pers, "camera required, no precomputed pers");
+    SGN_REQUIRE_NO_ROT(pt);
     SGN_REQUIRE(S_capacity >= 0 && S_capacity < (1 << 27), "S_capacity out of range");
     if (S_capacity == 0) return 0;
     AggArgs a{};
@@ -1022,6 +1056,23 @@ int sgn_aggregate_train_fwd(int32_t bpnet_layers, int32_t bpnet_dim, const void 
     auto kern = k_agg_rows<0, true>;
     if (ksb > 0) kern = ksb == KS_HID ? k_agg_rows<KS_HID, true> : k_agg_rows<ks_bp(BP_DIM), true>;
     hipLaunchKernelGGL(kern, dim3((unsigned)(wg < 256 ? wg : 256)), dim3(ROWS_TPB), 0, as_stream(stream), a);
+    SGN_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sgn_sample_viewdirs(const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
+                        float *d_out, sgn_stream_t stream) {
+    using namespace sgn;
+    SGN_REQUIRE(pt && q && d_out, "null argument");
+    SGN_REQUIRE(pt->rot && pt->raydir, "rot and raydir required");
+    SGN_REQUIRE(q->counters && q->work && q->samp_ray && q->pidx, "query outputs (counters, work, samp_ray, pidx) required");
+    SGN_REQUIRE(K >= 1 && K <= 16, "K = 1 .. 16");
+    SGN_REQUIRE(S_capacity >= 0 && S_capacity < (1 << 30), "S_capacity out of range");
+    if (S_capacity == 0 || pt->n_points <= 0) return 0;  // no neighbours: no work item
+    const int64_t blocks = (S_capacity + 255) / 256;
+    hipLaunchKernelGGL(k_sample_viewdirs, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, as_stream(stream),
+                       q->counters, q->work, q->samp_ray, q->pidx, pt->raydir, pt->rot, pt->n_points, S_capacity, K,
+                       d_out);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -440,10 +440,13 @@ static_assert(2 * ROWS16_LDS <= 163840, "LDS budget (16x16 rows, two workgroups 
 
 // row r's point record, its sample position and view direction (+ the caller's pers
 // coordinates on the compatibility path)
-template <bool PERS>
+// ROT (rotated neural points): v is the sample's rotated view direction (a.samp_v) and R the point's
+// Rw2c, read from the caller's [N,9] table (a.prot)
+template <bool PERS, bool ROT = false>
 struct Rec16 {
     float p[3], col[3], dir[3], cf, l[3], v[3];
     float pp[PERS ? 3 : 1], pl[PERS ? 3 : 1];  // the caller's pers coordinates (PointAggregator path only)
+    float R[ROT ? 9 : 1];
 };
 // Rows without a work item (ix.sval false: the tail of the work list, or a launch with no
 // samples at all, where samp_ray holds no written entry) read nothing.
@@ -451,19 +454,29 @@ struct Rec16 {
 // instead of ten dword gathers from four tables).
 // The nine loads of the record, sample position and ray direction are issued unconditionally (rows
 // without a work item or neighbour read the weight blob instead and select zeros), so a caller may
-// count them (REC16_LOADS) in a chunk boundary's vmcnt allowance.
+// count them (REC16_LOADS) in a chunk boundary's vmcnt allowance.  The rotated instantiation's loads of
+// R come on top and are NOT counted: an allowance only has to stay at or below the number of
+// vector-memory operations issued after the weight DMA (vmcnt retires in order, so with N or fewer
+// outstanding everything older than the N youngest has landed), and how many load instructions the
+// nine consecutive floats become is the compiler's choice.  The boundary then waits for some of them,
+// in the rotated kernel only.
 constexpr int REC16_LOADS = 9;
-template <bool PERS>
-__device__ __forceinline__ Rec16<PERS> load_rec16(const AggArgs &a, const RowIdx &ix) {
-    Rec16<PERS> r;
+template <bool PERS, bool ROT = false>
+__device__ __forceinline__ Rec16<PERS, ROT> load_rec16(const AggArgs &a, const RowIdx &ix) {
+    Rec16<PERS, ROT> r;
     const bool v = ix.sval;
     const int pid = ix.pid, s = ix.s, ray = ix.ray;
     const bool m = v && pid >= 0;
     const float *dummy = (const float *)a.blob;
     const f32x4 *rp = (const f32x4 *)(m ? a.rec + (int64_t)pid * REC16_FLOATS : dummy);
     const float *lp = v ? a.samp_locw + (int64_t)s * 3 : dummy;
-    const float *vp = v ? a.raydir + (int64_t)ray * 3 : dummy;
+    const float *vp = v ? (ROT ? a.samp_v + (int64_t)s * 3 : a.raydir + (int64_t)ray * 3) : dummy;
     const f32x4 q0 = rp[0], q1 = rp[1], q2 = rp[2];
+    if constexpr (ROT) {
+        const float *Rp = m ? a.prot + (int64_t)pid * 9 : dummy;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) r.R[c] = Rp[c];  // rows without a neighbour read blob words, selected away by m
+    }
     float l3[3], v3[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -642,14 +655,22 @@ struct Row16 {
     float d[6];
     float wgt, wn;
 };
-template <bool PERS>
-__device__ __forceinline__ Row16 row_math16(const Cam &cam, const Rec16<PERS> &rc, bool m, bool isA,
+template <bool PERS, bool ROT>
+__device__ __forceinline__ Row16 row_math16(const Cam &cam, const Rec16<PERS, ROT> &rc, bool m, bool isA,
                                             int nA, bool waveB) {
     Row16 o;
     const float dwx = __fsub_rn(rc.p[0], rc.l[0]), dwy = __fsub_rn(rc.p[1], rc.l[1]), dwz = __fsub_rn(rc.p[2], rc.l[2]);
-    o.d[0] = m ? dwx : 0.f;
-    o.d[1] = m ? dwy : 0.f;
-    o.d[2] = m ? dwz : 0.f;
+    if constexpr (ROT) {  // R_p (xyz_p - loc_s) for the encoding; the weights below keep the unrotated offset
+        float r0, r1, r2;
+        rot3(rc.R, dwx, dwy, dwz, r0, r1, r2);
+        o.d[0] = m ? r0 : 0.f;
+        o.d[1] = m ? r1 : 0.f;
+        o.d[2] = m ? r2 : 0.f;
+    } else {
+        o.d[0] = m ? dwx : 0.f;
+        o.d[1] = m ? dwy : 0.f;
+        o.d[2] = m ? dwz : 0.f;
+    }
     float xp, yp, zp, xl, yl, zl;
     if constexpr (PERS) {
         xp = rc.pp[0]; yp = rc.pp[1]; zp = rc.pp[2];
@@ -758,7 +779,8 @@ __device__ __forceinline__ Tiles grid_tiles(int ntiles) { return Tiles{(int)bloc
 // NS: row sets of 16 rows per wave.  NS = 2: 32 rows per wave, each LDS weight fragment pair feeds
 // six MFMAs (half the LDS reads and weight DMA per MFMA of NS = 1), one workgroup per CU and one
 // wave per SIMD (the accumulators of two layers, 256 registers, sit in AGPRs)
-template <int KB, bool PERS, bool SAVE = false, int NS = 1>
+// ROT: rotated neural points (Rec16, row_math16 and the block3 extras below)
+template <int KB, bool PERS, bool SAVE = false, int NS = 1, bool ROT = false>
 __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs a) {
     using Net = std::conditional_t<(KB > 0), NetR16SGT<KB>, NetR16T>;
     constexpr int LB = 2, L2 = KB ? 3 : 2, L3 = KB ? 4 : 3;
@@ -793,11 +815,11 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
     // and the P row (block3.2).  First tile: here.  Row set q of wave w: halves w 2 NS + 2 q (+ sc).
     const Tiles xt = grid_tiles((nslots + WGS - 1) / WGS);
     RowIdx nx[NS];
-    Rec16<PERS> rnext[NS];
+    Rec16<PERS, ROT> rnext[NS];
 #pragma unroll
     for (int q = 0; q < NS; ++q) {
         nx[q] = row_index16(a, xt.first * WGS + w * 2 * NS + 2 * q + sc, nslots, kk);
-        rnext[q] = load_rec16<PERS>(a, nx[q]);
+        rnext[q] = load_rec16<PERS, ROT>(a, nx[q]);
     }
     // P row of point pid into `dst`: natural unit order, tile t of lane group g at 16 t + 4 g, so the
     // 4 lanes of a row read one contiguous 64 B per load instruction
@@ -906,13 +928,13 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
             nslot[q] = tile + xt.step < xt.end ? hslot + xt.step * WGS : nslots;  // next tile's half
             ix[q] = nx[q];
             const bool m = ix[q].pid >= 0;
-            const Rec16<PERS> rc = rnext[q];
+            const Rec16<PERS, ROT> rc = rnext[q];
             // rows of the two segments (lane group 0 = rows 0..15): bits 8 h .. 8 h + 7 are half h's
             mrowA[q] = __ballot(ix[q].sval && ix[q].a);
             mrowB[q] = __ballot(ix[q].sval && !ix[q].a);
             const int nA0 = __popc((uint32_t)mrowA[q] & 0xFFu), nA1 = __popc(((uint32_t)mrowA[q] >> 8) & 0xFFu);
             const bool waveB = (mrowB[q] & 0xFFFFull) != 0;  // wave-uniform: a B sample in either half
-            rw[q] = row_math16<PERS>(cam, rc, m, ix[q].a, sc ? nA1 : nA0, waveB);
+            rw[q] = row_math16<PERS, ROT>(cam, rc, m, ix[q].a, sc ? nA1 : nA0, waveB);
             nA[q] = __popcll((mrowA[q] >> hsh) & 0xFFull);
             nB[q] = __popcll((mrowB[q] >> hsh) & 0xFFull);
             // SAVE: the row's pidx index s * K + k (from the slot's row table entry s * 8 + k), or its
@@ -929,13 +951,14 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
             }
             {   // block3 extra channels: colour, dir - v, <dir, v> (:639-652), lane group 0
                 const bool e = g == 0 && m;
-                float u[8];
+                float u[8], pd[3] = {rc.dir[0], rc.dir[1], rc.dir[2]};
+                if constexpr (ROT) rot3(rc.R, pd[0], pd[1], pd[2], pd[0], pd[1], pd[2]);  // R_p dir_p
                 u[0] = e ? rc.col[0] : 0.f; u[1] = e ? rc.col[1] : 0.f; u[2] = e ? rc.col[2] : 0.f;
-                u[3] = e ? __fsub_rn(rc.dir[0], rc.v[0]) : 0.f;
-                u[4] = e ? __fsub_rn(rc.dir[1], rc.v[1]) : 0.f;
-                u[5] = e ? __fsub_rn(rc.dir[2], rc.v[2]) : 0.f;
-                u[6] = e ? __fadd_rn(__fadd_rn(__fmul_rn(rc.dir[0], rc.v[0]), __fmul_rn(rc.dir[1], rc.v[1])),
-                                     __fmul_rn(rc.dir[2], rc.v[2])) : 0.f;
+                u[3] = e ? __fsub_rn(pd[0], rc.v[0]) : 0.f;
+                u[4] = e ? __fsub_rn(pd[1], rc.v[1]) : 0.f;
+                u[5] = e ? __fsub_rn(pd[2], rc.v[2]) : 0.f;
+                u[6] = e ? __fadd_rn(__fadd_rn(__fmul_rn(pd[0], rc.v[0]), __fmul_rn(pd[1], rc.v[1])),
+                                     __fmul_rn(pd[2], rc.v[2])) : 0.f;
                 u[7] = 0.f;
                 ext[q] = split8_unit(u);
             }
@@ -1072,7 +1095,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
             if constexpr (decltype(c)::value == 0) {
 #pragma unroll
                 for (int q = 0; q < NS; ++q) {
-                    rnext[q] = load_rec16<PERS>(a, nx[q]);
+                    rnext[q] = load_rec16<PERS, ROT>(a, nx[q]);
                     ce[q] = *(const int2 *)(a.slots + (eslot[q] < nslots ? eslot[q] : 0));
                 }
             }
@@ -1121,6 +1144,10 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
                 if constexpr (PERS) asm volatile("" : "+v"(rnext[q].pp[c]), "+v"(rnext[q].pl[c]));
             }
             asm volatile("" : "+v"(rnext[q].cf));
+            if constexpr (ROT) {
+#pragma unroll
+                for (int c = 0; c < 9; ++c) asm volatile("" : "+v"(rnext[q].R[c]));
+            }
         }
         {   // the rest of the epilogue; the next tile's P rows (see accA) go out first, into block3.2's
             // consumed input registers, and land under it
@@ -1288,6 +1315,7 @@ struct ColorArgs {
     float *feat;
     int32_t *range_flag;  // set to 1 when a sample's decoded features are not finite (fp16 range exceeded)
     int32_t item0, n_items;
+    const float *viewdir;  // ROT: [S,3] the sample's rotated view direction (sgn_sample_viewdirs)
 };
 // ---- colour MLP, 16x16 (2 waves per SIMD): 8 waves x 16 samples per 128-sample tile --------
 // Lane (sample r = l & 15, group g = l >> 4).  Colour 0's k-step s < 8 takes f_s units 32 s + 8 g + j
@@ -1299,6 +1327,8 @@ constexpr int YC_OFF = NSLOT * SPC * PAIR, TPBC = NWC * 64;
 constexpr int COL16_LDS = YC_OFF + N_Y32 * 4;
 static_assert(COL16_LDS <= 163840, "LDS budget (colour, one workgroup per CU)");
 
+// ROT: the view direction is the sample's rotated one (a.viewdir[s]) instead of its ray's
+template <bool ROT = false>
 __global__ __launch_bounds__(TPBC, 1) void k_color16(ColorArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[COL16_LDS];
     const int lane = threadIdx.x & 63;
@@ -1348,7 +1378,7 @@ __global__ __launch_bounds__(TPBC, 1) void k_color16(ColorArgs a) {
     auto load_ray = [&]() { rn = a.samp_ray[sn]; };
     auto load_dir = [&]() {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) vd[c] = a.raydir[(int64_t)rn * 3 + c];
+        for (int c = 0; c < 3; ++c) vd[c] = ROT ? a.viewdir[(int64_t)sn * 3 + c] : a.raydir[(int64_t)rn * 3 + c];
     };
     {
         const int item = a.item0 + blockIdx.x * (16 * NWC) + w * 16 + r;
@@ -1575,8 +1605,11 @@ int32_t *ws_tail(void *d_workspace, size_t workspace_bytes) {
 namespace {
 // k_rows16 of a network variant: KB = block2_bpnet.0's k-steps (0: base, 8: bpnet_dim 0, 11: dim 96)
 template <bool PERS, bool SAVE, int NS>
-auto rows_kernel(int ksb) {
+auto rows_kernel(int ksb, bool rot = false) {
     using namespace sgn;
+    if constexpr (!PERS && !SAVE && NS == 2) {
+        if (rot) return x3::k_rows16<0, false, false, 2, true>;  // rotated points: the base network's inference rows
+    }
     return ksb == 0 ? x3::k_rows16<0, PERS, SAVE, NS> : ksb == mlp::KS_HID ? x3::k_rows16<8, PERS, SAVE, NS>
                                                                             : x3::k_rows16<11, PERS, SAVE, NS>;
 }
@@ -1597,6 +1630,8 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
     SGN_REQUIRE(K >= 1 && K <= 8, "the fp32 MFMA aggregator takes K = 1 .. 8 neighbours per sample");
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir, "camera (campos, camrotc2w, raydir) required");
     SGN_REQUIRE((pt->pers == nullptr) == (pt->samp_pers == nullptr), "pers and samp_pers go together");
+    SGN_REQUIRE_ROT(pt, ksb);
+    SGN_REQUIRE(!(pt->rot && z), "rot (per-point Rw2c) is not supported by the training forward");
     SGN_REQUIRE(S_capacity >= 0 && S_capacity < (1 << 30), "S_capacity out of range");
     SGN_REQUIRE(((uintptr_t)d_workspace & 15) == 0 && ((uintptr_t)d_point_proj & 15) == 0, "16-byte alignment required");
     hipStream_t st = as_stream(stream);
@@ -1638,7 +1673,7 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
     // the fp16-range flag covers the samples of this call's colour stage (cleared with its first chunk)
     if (stages & 2) SGN_CHECK_HIP(hipMemsetAsync(tail + 1, 0, 4, st));
     x3::ColorArgs c{q->counters, q->work, q->samp_ray, pt->raydir, d_packed, (const float *)d_workspace, d_out_feat,
-                    tail + 1, 0, 0};
+                    tail + 1, 0, 0, pt->samp_viewdir};
     for (int64_t i0 = 0; i0 < S_capacity; i0 += chunk) {
         const int64_t n = S_capacity - i0 < chunk ? S_capacity - i0 : chunk;
         a.item0 = c.item0 = (int32_t)i0;
@@ -1657,14 +1692,14 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
             const int ns = z ? 1 : 2;
             auto kern = z ? rows_kernel<false, true, 1>(ksb)              // <PERS, SAVE, NS>
                           : pt->pers ? rows_kernel<true, false, 2>(ksb)  // the caller's pers coordinates
-                                     : rows_kernel<false, false, 2>(ksb);
+                                     : rows_kernel<false, false, 2>(ksb, pt->rot != nullptr);
             const int64_t wg16 = (n + x3::WG16_SAMPLES * ns - 1) / (x3::WG16_SAMPLES * ns),
                           wmax = ns == 1 ? 256 * (8 / x3::NWR) : 256;
             hipLaunchKernelGGL(kern, dim3((unsigned)(wg16 < wmax ? wg16 : wmax)), dim3(x3::TPBR), 0, st, a);
         }
         if (stages & 2) {
             const int64_t wgc = (n + 16 * x3::NWC - 1) / (16 * x3::NWC), wcmax = 256;
-            hipLaunchKernelGGL(x3::k_color16, dim3((unsigned)(wgc < wcmax ? wgc : wcmax)), dim3(x3::TPBC), 0, st, c);
+            hipLaunchKernelGGL(pt->rot ? x3::k_color16<true> : x3::k_color16<false>, dim3((unsigned)(wgc < wcmax ? wgc : wcmax)), dim3(x3::TPBC), 0, st, c);
         }
     }
     SGN_CHECK_HIP(hipGetLastError());

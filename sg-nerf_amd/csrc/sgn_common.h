@@ -30,6 +30,20 @@ const char *get_error();
         }                                                               \
     } while (0)
 
+// Rotated neural points (sgn_point_tables::rot, the per-point Rw2c): the base network's inference
+// entries take them (with samp_viewdir, and without the caller's pers coordinates); every other entry
+// that builds aggregator inputs refuses them instead of rendering them unrotated.
+#define SGN_REQUIRE_NO_ROT(pt) \
+    SGN_REQUIRE(!(pt)->rot, "rot (per-point Rw2c) is not supported by this entry (inference of the base network only)")
+#define SGN_REQUIRE_ROT(pt, ksb)                                                                                  \
+    do {                                                                                                          \
+        if ((pt)->rot) {                                                                                          \
+            SGN_REQUIRE((ksb) == 0, "rot (per-point Rw2c) is built for the base network only (bpnet_layers = 0)"); \
+            SGN_REQUIRE((pt)->samp_viewdir, "rot needs samp_viewdir (sgn_sample_viewdirs)");                      \
+            SGN_REQUIRE(!(pt)->pers, "rot does not combine with the caller's pers coordinates");                  \
+        }                                                                                                         \
+    } while (0)
+
 inline hipStream_t as_stream(sgn_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- parity-mode reservoir RNG (identical to oracle/query_ref.c) ----------

@@ -1548,6 +1548,7 @@ int sgn_train_row_inputs(const sgn_point_tables *pt, const sgn_query_out *q, int
     SGN_REQUIRE(pt && q && d_row_off && d_counts && d_x0 && d_ext && d_rw && d_vpe, "null argument");
     SGN_REQUIRE(K >= 1 && K <= 8, "K = 1 .. 8");
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir && !pt->pers, "camera required, no precomputed pers");
+    SGN_REQUIRE_NO_ROT(pt);
     SGN_REQUIRE(((uintptr_t)d_x0 & 15) == 0 && ((uintptr_t)d_rw & 7) == 0, "aligned x0 / rw required");
     const RowArgs a = row_args(pt, q, K, d_row_off, d_counts);
     hipStream_t st = as_stream(stream);
@@ -1613,6 +1614,7 @@ int sgn_train_row_head(const sgn_point_tables *pt, const sgn_query_out *q, int32
                     d_amax && d_part,
                 "null argument");
     SGN_REQUIRE(K >= 1 && K <= 8, "K = 1 .. 8");
+    SGN_REQUIRE_NO_ROT(pt);
     const RowArgs a = row_args(pt, q, K, d_row_off, d_counts);
     hipLaunchKernelGGL(k_row_head, dim3(ROW_HEAD_BLOCKS), dim3(TPB), 0, as_stream(stream), a, d_z4_delta4, d_dfs,
                        (const float4 *)d_dfeat, (const float2 *)d_rw, d_wa, d_ba, d_gconf, d_amax, d_part);
@@ -1628,6 +1630,7 @@ int sgn_train_row_tail(const sgn_point_tables *pt, const sgn_query_out *q, int32
     SGN_REQUIRE(pt && q && d_row_off && d_counts && d_dx0 && d_dext && grads, "null argument");
     SGN_REQUIRE(grads->embedding && grads->color && grads->dir, "null gradient outputs");
     SGN_REQUIRE(K >= 1 && K <= 8, "K = 1 .. 8");
+    SGN_REQUIRE_NO_ROT(pt);
     const RowArgs a = row_args(pt, q, K, d_row_off, d_counts);
     hipLaunchKernelGGL(k_row_tail, dim3(ROW_GRID), dim3(TPB), 0, as_stream(stream), a, d_dx0, d_dext, grads->embedding,
                        grads->color, grads->dir);

@@ -116,18 +116,43 @@ class HipPointsVolumetricModel:
                    aggregator_state=None):
         """mvs_points_volumetric_model.py:191-199 -> neural_points.py:575-600 (same argument names
         and order); also takes the aggregator weights when no checkpoint is loaded.  In training
-        the optimizers are rebuilt over the new points."""
+        the optimizers are rebuilt over the new points.
+
+        Rw2c ([3,3] or [N,3,3], one matrix per point) is the points' rotation, rendered by the rotated
+        kernels.  editing=True stays refused here, as it always was: edited clouds (run/editing.py:181-212)
+        go through editing_set_points below, which never builds an optimizer."""
         if editing:
-            raise NotImplementedError("set_points(editing=True) (point-cloud editing) is outside the HIP hot path")
+            raise NotImplementedError("set_points(editing=True) is refused: pass the edited cloud (with its Rw2c) to "
+                                      "editing_set_points(), which sets it for rendering only")
+        self._set_points(points_xyz, points_feats, points_embedding, points_label, points_color, points_dir,
+                         points_conf, Rw2c, False, aggregator_state)
+
+    def editing_set_points(self, points_xyz, points_embedding, points_color=None, points_dir=None, points_conf=None,
+                           Rw2c=None, eulers=None, points_feats=None, points_label=None, aggregator_state=None):
+        """neural_points.py:667-681 (NeuralPoints.editing_set_points, which the reference's
+        set_points(editing=True) reaches; run/editing.py:181-212 calls it with the parts it cut out of several
+        checkpoints and moved, Rw2c one matrix per point): opt.default_conf in (0, 1] overrides points_conf, and
+        nothing is trainable -- no optimizer is built, even in training mode."""
+        self._set_points(points_xyz, points_feats, points_embedding, points_label, points_color, points_dir,
+                         points_conf, Rw2c, True, aggregator_state)
+
+    def _set_points(self, points_xyz, points_feats, points_embedding, points_label, points_color, points_dir,
+                    points_conf, Rw2c, editing, aggregator_state):
         if points_embedding is None:
             raise ValueError("set_points: points_embedding is required")
         if points_conf is None:
             points_conf = torch.ones(points_embedding.shape[:-1] + (1,), dtype=torch.float32)
+        if editing:
+            dc = float(getattr(self.opt, "default_conf", -1.0) or 0.0)
+            if 0.0 < dc <= 1.0:
+                points_conf = torch.ones_like(torch.as_tensor(points_conf), dtype=torch.float32) * dc
         for name, t in (("points_color", points_color), ("points_dir", points_dir)):
             if t is None:
                 raise NotImplementedError(f"set_points without {name}: the MFMA aggregator's inputs include it")
         self.neural_points = NeuralPoints(points_xyz, points_embedding, points_color, points_dir, points_conf,
-                                          self.device, points_feats=points_feats, points_label=points_label)
+                                          self.device, points_feats=points_feats, points_label=points_label,
+                                          Rw2c=Rw2c)
+        self._check_rotation()
         if aggregator_state is not None or self.net_ray_marching is None:
             if aggregator_state is None:
                 raise ValueError("set_points: aggregator_state required before the first render")
@@ -136,8 +161,23 @@ class HipPointsVolumetricModel:
         else:
             self._sync_weights()
             self.net_ray_marching.neural_points = self.neural_points
-        if self.is_train:
+        if editing:
+            self.trainer = None
+            self.optimizers = []
+        elif self.is_train:
             self.setup_optimizer(self.opt)
+
+    def _check_rotation(self, training=False):
+        """What a non-identity Rw2c does not combine with: the SG variant (block2_bpnet) and training."""
+        p = self.neural_points
+        if p is None or not p.rotated():
+            return
+        if self.opts.bpnet_variant[0]:
+            raise NotImplementedError("a non-identity Rw2c with the SG options (shading_feature_mlp_layer2_bpnet): "
+                                      "rotated points are built for the base viewmlp only")
+        if training:
+            raise NotImplementedError("training with a non-identity Rw2c is not supported: rotated (edited) "
+                                      "point clouds render only")
 
     # -- training (mvs_points_volumetric_model.py:47-141, base_model.py:138-160) -----------------
     def setup_optimizer(self, opt):
@@ -146,6 +186,7 @@ class HipPointsVolumetricModel:
         from .train_hip import HipTrainer
         if self.neural_points is None or self.net_ray_marching is None:
             raise RuntimeError("setup_optimizer: no neural points / aggregator weights yet")
+        self._check_rotation(training=True)
         self._sync_weights()
         npnt = self.neural_points
         params = PointParams(npnt.xyz, npnt.points_embeding, npnt.points_color, npnt.points_dir, npnt.points_conf,
@@ -218,18 +259,30 @@ class HipPointsVolumetricModel:
         self.neural_points = NeuralPoints(p.xyz[mask], p.points_embeding[:, mask], p.points_color[:, mask],
                                           p.points_dir[:, mask], p.points_conf[:, mask], self.device,
                                           points_feats=keep(p.points_feats), points_label=keep(p.points_label),
-                                          bpnet_points_embedding=keep(p.bpnet_points_embedding))
+                                          bpnet_points_embedding=keep(p.bpnet_points_embedding),
+                                          Rw2c=p.Rw2c[mask] if p.Rw2c.dim() == 3 else p.Rw2c)  # :540-542
         self.net_ray_marching.neural_points = self.neural_points
         return int((~mask).sum())
 
-    def grow_points(self, add_xyz, add_embedding, add_color, add_dir, add_conf, add_label=None, **unused):
+    def grow_points(self, add_xyz, add_embedding, add_color, add_dir, add_conf, add_label=None, add_Rw2c=None,
+                    **unused):
         """neural_points.py:546-572: append points (embedding/colour/dir/conf given as [M, C]).
         Labels are appended when both sides have them (:550); points_feats is kept as it is,
         as the reference keeps it.  The BPNet embedding gets zero rows for the new points (the
         reference leaves it at the old length, which its index_select at neural_points.py:972
-        would then overrun)."""
+        would then overrun).  A per-point Rw2c gets add_Rw2c [M,3,3] for the new points, or identity
+        rows without it (the reference's torch.cat at neural_points.py:570-572 would fail on None); a
+        [3,3] Rw2c covers the new points as it is."""
         self._sync_weights()
         p = self.neural_points
+        Rw2c = p.Rw2c
+        if Rw2c.dim() == 3:
+            m = torch.as_tensor(add_xyz).reshape(-1, 3).shape[0]
+            add = (torch.eye(3, dtype=torch.float32, device=Rw2c.device).expand(m, 3, 3) if add_Rw2c is None
+                   else torch.as_tensor(add_Rw2c).to(Rw2c.device, torch.float32).reshape(m, 3, 3))
+            Rw2c = torch.cat([Rw2c, add], 0)
+        elif add_Rw2c is not None:
+            raise ValueError("grow_points: add_Rw2c given, but the points' Rw2c is one [3,3] matrix for every point")
         f = lambda t, c: torch.as_tensor(t).to(self.device, torch.float32).reshape(1, -1, c)  # noqa: E731
         label = p.points_label
         bp = p.bpnet_points_embedding
@@ -245,7 +298,7 @@ class HipPointsVolumetricModel:
             torch.cat([p.points_embeding, f(add_embedding, p.points_embeding.shape[-1])], 1),
             torch.cat([p.points_color, f(add_color, 3)], 1), torch.cat([p.points_dir, f(add_dir, 3)], 1),
             torch.cat([p.points_conf, f(add_conf, 1)], 1), self.device, points_feats=p.points_feats,
-            points_label=label, bpnet_points_embedding=bp)
+            points_label=label, bpnet_points_embedding=bp, Rw2c=Rw2c)
         self.net_ray_marching.neural_points = self.neural_points
         if self.is_train and getattr(self, "trainer", None) is not None:
             self.setup_optimizer(self.opt)
@@ -292,6 +345,7 @@ class HipPointsVolumetricModel:
 
     def optimize_parameters(self, backward=True, total_steps=0):
         """neural_points_volumetric_model.py:320-331: forward, losses, backward, both Adam steps."""
+        self._check_rotation(training=True)
         if getattr(self, "trainer", None) is None:
             self.setup_optimizer(self.opt)
         if self.trainer is None:  # SG with predict_semantic: setup_optimizer waits for the embedding
@@ -445,5 +499,6 @@ class HipPointsVolumetricModel:
         path = os.path.join(directory, f"{epoch}_net_ray_marching.pth")
         sd = torch.load(path, map_location="cpu", weights_only=True)
         self.neural_points = NeuralPoints.from_state_dict(sd, self.device)
+        self._check_rotation()
         self.net_ray_marching = NeuralPointsRayMarching(self.neural_points, strip_prefix(sd), self.opts, self.device)
         return path

@@ -55,10 +55,14 @@ class NeuralPoints:
 
     The semantic attributes ride along: points_feats [N,3] (the init cloud's RGB in 0..255,
     BPNet's input, scannet_ft_dataset.py:482 / neural_points.py:589-590), points_label [N,1]
-    and bpnet_points_embedding [1,N,96] (neural_points.py:653-665)."""
+    and bpnet_points_embedding [1,N,96] (neural_points.py:653-665).
+
+    Rw2c is the reference's point rotation (neural_points.py:967): one [3,3] matrix or [N,3,3], one
+    per point (what scene editing produces, run/editing.py:181-212).  It goes to the kernels through
+    `tables()`; identity runs the unrotated kernels."""
 
     def __init__(self, xyz, points_embeding, points_color, points_dir, points_conf, device="cuda",
-                 points_feats=None, points_label=None, bpnet_points_embedding=None):
+                 points_feats=None, points_label=None, bpnet_points_embedding=None, Rw2c=None):
         dev = torch.device(device)
         f = dict(dtype=torch.float32, device=dev)
         self.xyz = torch.as_tensor(xyz).to(**f).reshape(-1, 3)
@@ -67,7 +71,7 @@ class NeuralPoints:
         self.points_color = torch.as_tensor(points_color).to(**f).reshape(1, n, 3)
         self.points_dir = torch.as_tensor(points_dir).to(**f).reshape(1, n, 3)
         self.points_conf = torch.as_tensor(points_conf).to(**f).reshape(1, n, 1)
-        self.Rw2c = torch.eye(3, **f)
+        self.Rw2c = torch.eye(3, **f) if Rw2c is None else self._check_Rw2c(Rw2c, n, dev)
         self.device = dev
         # SG-NeRF semantic attributes (neural_points.py:653-665), set by set_bpnet_feats
         self.bpnet_points_embedding = None  # [1,N,96], detached
@@ -80,6 +84,17 @@ class NeuralPoints:
             self.bpnet_points_embedding = torch.as_tensor(bpnet_points_embedding).detach().to(**f).reshape(1, n, -1)
         self._tables = None
         self._key = None
+
+    @staticmethod
+    def _check_Rw2c(Rw2c, n, dev):
+        r = torch.as_tensor(Rw2c).detach().to(dev, torch.float32)
+        if tuple(r.shape) not in ((3, 3), (n, 3, 3)):
+            raise ValueError(f"Rw2c has shape {tuple(r.shape)}: expected [3,3] or [{n},3,3]")
+        return r
+
+    def rotated(self):
+        """Whether Rw2c is anything but exact identity (per point or global)."""
+        return not torch.equal(self.Rw2c, torch.eye(3, dtype=torch.float32, device=self.Rw2c.device).expand_as(self.Rw2c))
 
     def set_bpnet_feats(self, points_label_prob, points_label, bpnet_points_embedding):
         """neural_points.py:653-665: per-point BPNet labels and (first call only) embedding."""
@@ -101,7 +116,7 @@ class NeuralPoints:
                 points_feats=o("points_feats"), points_label=o("points_label"),
                 bpnet_points_embedding=o("bpnet_points_embedding"))
         if o("Rw2c") is not None:
-            p.Rw2c = torch.as_tensor(o("Rw2c")).to(p.device, torch.float32)
+            p.Rw2c = cls._check_Rw2c(o("Rw2c"), p.xyz.shape[0], p.device)
         return p
 
     @classmethod
@@ -119,7 +134,7 @@ class NeuralPoints:
         return sd
 
     def _version_key(self):
-        ts = (self.xyz, self.points_embeding, self.points_color, self.points_dir, self.points_conf)
+        ts = (self.xyz, self.points_embeding, self.points_color, self.points_dir, self.points_conf, self.Rw2c)
         if self.bpnet_points_embedding is not None:
             ts = ts + (self.bpnet_points_embedding,)
         return tuple((t.data_ptr(), tuple(t.shape), t._version) for t in ts)
@@ -130,15 +145,19 @@ class NeuralPoints:
             if self.points_embeding.shape[-1] != 32:
                 raise NotImplementedError("the MFMA aggregator is built for point_features_dim = 32")
             self._tables = PointTables(self.xyz, self.points_embeding, self.points_color, self.points_dir,
-                                       self.points_conf, self.device, self.bpnet_points_embedding)
+                                       self.points_conf, self.device, self.bpnet_points_embedding, self.Rw2c)
             self._key = key
         return self._tables
 
-    def set_points(self, xyz, points_embeding, points_color=None, points_dir=None, points_conf=None):
-        """neural_points.py:520-572 (replace the cloud; grid is rebuilt on next query)."""
+    def set_points(self, xyz, points_embeding, points_color=None, points_dir=None, points_conf=None, Rw2c=None):
+        """neural_points.py:520-572 (replace the cloud; grid is rebuilt on next query).  Rw2c: [3,3] or
+        [N,3,3] for the new cloud (:540-542); None keeps a [3,3] one and resets a per-point one, whose
+        rows belonged to the old points."""
+        if Rw2c is None and self.Rw2c.dim() == 2:
+            Rw2c = self.Rw2c
         self.__init__(xyz, points_embeding, points_color if points_color is not None else self.points_color,
                       points_dir if points_dir is not None else self.points_dir,
-                      points_conf if points_conf is not None else self.points_conf, self.device)
+                      points_conf if points_conf is not None else self.points_conf, self.device, Rw2c=Rw2c)
 
 
 # ----------------------------------------------------------------------------------
@@ -344,6 +363,11 @@ class PointAggregator:
                 sampled_embedding, sampled_xyz_pers, sampled_xyz, sample_pnt_mask, sample_loc, sample_loc_w,
                 sample_ray_dirs, vsize, grid_vox_sz):
         dev = self.device
+        if sampled_Rw2c is not None:
+            r = torch.as_tensor(sampled_Rw2c)
+            if r.shape[-2:] != (3, 3) or not torch.equal(r.float(), torch.eye(3, device=r.device).expand_as(r)):
+                raise NotImplementedError("PointAggregator.forward: a non-identity sampled_Rw2c is not supported on this "
+                                          "compatibility path (rotated points render through NeuralPointsRayMarching)")
         shp = sample_loc_w.shape[:-1]  # [1, R, SR]
         K = sample_pnt_mask.shape[-1]
         if not (1 <= K <= 8):

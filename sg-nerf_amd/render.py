@@ -30,9 +30,13 @@ class RenderOut:
 
 
 class PointTables:
-    """Device-resident neural point cloud (contiguous fp32 tables)."""
+    """Device-resident neural point cloud (contiguous fp32 tables).
 
-    def __init__(self, xyz, embedding, color, dir, conf, device, bpnet=None):
+    `rot`: the reference's Rw2c (neural_points.py:967), [N,3,3] per point or one [3,3] for every
+    point -> the [N,9] table the rotated kernels read.  A table that is exactly identity is kept as
+    None: such clouds run the stock kernels, bit for bit."""
+
+    def __init__(self, xyz, embedding, color, dir, conf, device, bpnet=None, rot=None):
         def t(x, cols):
             x = torch.as_tensor(x).reshape(-1, cols)
             return x.to(device=device, dtype=torch.float32).contiguous()
@@ -46,6 +50,21 @@ class PointTables:
         self.bpnet32 = None
         if bpnet is not None:
             self.set_bpnet(bpnet)
+        self.rot = self._rot_table(rot, device)
+
+    def _rot_table(self, rot, device):
+        if rot is None:
+            return None
+        r = torch.as_tensor(rot).detach().to(dtype=torch.float32)
+        if r.numel() == 9:
+            r = r.reshape(1, 3, 3)
+        elif r.numel() == 9 * self.n and r.dim() >= 2:
+            r = r.reshape(self.n, 3, 3)
+        else:
+            raise ValueError(f"Rw2c has shape {tuple(r.shape)}: expected [3,3] or [{self.n},3,3]")
+        if torch.equal(r, torch.eye(3, dtype=torch.float32, device=r.device).expand_as(r)):
+            return None
+        return r.expand(self.n, 3, 3).reshape(self.n, 9).to(device=device).contiguous()
 
     def set_bpnet(self, bpnet):
         """SG: bpnet_points_embedding [N, 96] (neural_points.py:653-665, detached there too)
@@ -61,7 +80,8 @@ class PointTables:
 
     @classmethod
     def from_cloud(cls, pc, device):
-        return cls(pc.xyz, pc.embedding, pc.color, pc.dir, pc.conf, device, getattr(pc, "bpnet", None))
+        return cls(pc.xyz, pc.embedding, pc.color, pc.dir, pc.conf, device, getattr(pc, "bpnet", None),
+                   getattr(pc, "rot", None))
 
 
 class HipRenderer:
@@ -108,7 +128,10 @@ class HipRenderer:
             self.wnorm = None
             self.blendw = None
             self.probe = None
+            self.viewdir = None   # [cap,3] rotated view direction per sample (rotated points only)
             self._cap = (R, cap)
+        if self.points.rot is not None and self.viewdir is None:
+            self.viewdir = torch.zeros(self._cap[1], 3, dtype=torch.float32, device=self.device)
 
     def _flag(self):
         off = int(_lib.lib().sgn_aggregate_flag_offset_f32(self.agg_ws.numel()))
@@ -201,6 +224,14 @@ class HipRenderer:
         qo = q.abi()
         cap = R * o.SR
         nl, dim = self.variant
+        if self.points.rot is not None:
+            # rotated points (per-point Rw2c): the samples' rotated view directions, once per frame
+            if nl:
+                raise NotImplementedError("a non-identity Rw2c is built for the base viewmlp only, not block2_bpnet (SG)")
+            pt.rot = self.points.rot.data_ptr()
+            _lib.check(L.sgn_sample_viewdirs(ctypes.byref(pt), ctypes.byref(qo), cap, o.K, _lib.ptr(self.viewdir), st),
+                       "sgn_sample_viewdirs")
+            pt.samp_viewdir = self.viewdir.data_ptr()
         if dim and self.points.bpnet16 is None:
             raise ValueError("block2_bpnet with predict_semantic = 1 needs the points' BPNet embedding (set_bpnet)")
         bp = (_lib.ptr(self.points.bpnet32) if self.f32 else _lib.ptr(self.points.bpnet16)) if dim else None

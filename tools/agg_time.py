@@ -1,6 +1,8 @@
 """Timing probe (not product): config-2 frames (synth-room 1.2 M points, 800x800, SR 64) at one
 precision; prints one JSON line with per-stage HIP-event medians.  Usage:
-    python tools/agg_time.py [f32|f16] [frames]"""
+    python tools/agg_time.py [f32|f16] [frames]
+SGN_ROT=1: the same frames with a rotation per point (Rw2c from a four-matrix palette: the rotated kernels;
+sgn_sample_viewdirs runs between the "query" and "proj" marks, so its time is in the query stage)."""
 import json
 import os
 import sys
@@ -22,7 +24,16 @@ dev = "cuda:0"
 pc = scene.synth_room(1_200_000, seed=0)
 mlp = init_mlp(0, bias_std=0.01)
 mlp["alpha_branch.0.bias"] = mlp["alpha_branch.0.bias"] + 50.0
-r = HipRenderer(PointTables.from_cloud(pc, dev), mlp, HotPathOpts(SR=64, precision=prec), dev)
+rw2c = None
+if os.environ.get("SGN_ROT", "0") == "1":
+    def _axis(a, deg):
+        a = np.asarray(a, np.float64) / np.linalg.norm(a)
+        k = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+        return np.eye(3) + np.sin(np.deg2rad(deg)) * k + (1 - np.cos(np.deg2rad(deg))) * (k @ k)
+    pal = np.stack([np.eye(3), _axis((0, 0, 1), 40.0), _axis((1, 2, 3), 75.0), _axis((-1, 1, 0.5), 170.0)]).astype(np.float32)
+    rw2c = torch.from_numpy(pal[np.random.default_rng(5).integers(0, 4, pc.xyz.shape[0])])
+r = HipRenderer(PointTables(pc.xyz, pc.embedding, pc.color, pc.dir, pc.conf, dev, rot=rw2c), mlp,
+                HotPathOpts(SR=64, precision=prec), dev)
 # SGN_RAY_ORDER=B (B > 0): rays fed in B x B pixel blocks (block-major) instead of row-major
 blk = int(os.environ.get("SGN_RAY_ORDER", "0"))
 perm = None
@@ -59,4 +70,5 @@ res["frame"] = float(np.median([e["query"].elapsed_time(e["end"]) for e in ev]))
 res["prec"] = prec
 res["lib"] = os.environ.get("SGN_VARIANT", "base")
 res["ray_block"] = blk
+res["rot"] = rw2c is not None
 print(json.dumps(res), flush=True)
