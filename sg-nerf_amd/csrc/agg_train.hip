@@ -20,8 +20,9 @@
 //   delta1 = (W1^T delta2) * LReLU'(h1), d x0 = W0^T delta1 -> d feat through PE(feat)
 // The accumulator of one product is converted in registers into the B operand of the next
 // (the k permutation lives in the transposed weight blob, as in the forward).  Weight
-// gradients dW_l = delta_l^T x_l are plain GEMMs over the saved [rows][C] tiles (host side,
-// hipBLASLt); the deltas are written for them.  Gradients are computed with a loss scale
+// gradients dW_l = delta_l^T x_l are GEMMs over the saved [rows][C] tiles, launched by the host
+// (sgn_f16_weight_grad, dw_f16.hip); the deltas are written for them, masked rows as +-0, since those
+// GEMMs sum over all 8 n rows.  Gradients are computed with a loss scale
 // (device scalar) so fp16 deltas keep their precision; point gradients leave unscaled.
 #include <vector>
 
