@@ -341,6 +341,9 @@ typedef struct {
     void *h4;                 /* fp16 [rows][256] block3.2 outputs (same order) */
     float *dza;               /* [rows] scaled d loss / d alpha-branch logit */
 } sgn_agg_deltas;
+/* A NULL member is a frozen tensor (opt.feat_grad / color_grad / dir_grad / conf_grad = 0,
+ * neural_points.py:410-416): its gradient is neither computed nor written.  All four non-NULL is
+ * the contract of every earlier revision, unchanged. */
 typedef struct {
     float *embedding, *color, *dir, *conf;  /* [N,32] [N,3] [N,3] [N]: accumulated (+=), unscaled */
 } sgn_point_grads;
@@ -353,7 +356,10 @@ int sgn_aggregate_train_fwd(int32_t bpnet_layers, int32_t bpnet_dim, const void 
                             void *d_h2b, sgn_stream_t stream);
 /* Backward for n_items work items: d_dfs f32 [n_items][256], d_dalpha f32 [n_items] (d loss w.r.t.
  * the blended features / alpha), d_scale: device scalar loss scale.  K: neighbours per sample of
- * q->pidx, 1 .. 8, as in the forward. */
+ * q->pidx, 1 .. 8, as in the forward.  NULL members of grads: frozen tensors -- only the trained
+ * tensors' atomics are issued, and with grads->embedding NULL block1.0's input-gradient product
+ * (W0^T delta1 and the PE(feat) chain) is not computed; the deltas are written either way (all four
+ * NULL included: the weight gradients read them). */
 int sgn_aggregate_backward(int32_t bpnet_layers, int32_t bpnet_dim, const sgn_point_tables *pt,
                            const sgn_query_out *q, int32_t n_items, int32_t K, const void *d_packed_mlp,
                            const void *d_tblob, const sgn_agg_saved *saved, const void *d_h2b, const float *d_dfs,
@@ -634,13 +640,17 @@ int sgn_train_colour_head_bwd(const sgn_query_out *q, const int32_t *d_counts, c
  * = d loss / d f_s; d_dfeat.x = d loss / d alpha_s; d_rw from sgn_train_row_inputs; d_wa [256],
  * d_ba [1] alpha_branch.0; d_gconf[N] += d conf (straight-through clamp, :863-865); *d_amax =
  * max |delta4|; d_part = alpha_branch.0's weight / bias gradient, sgn_train_head_partial_floats(1)
- * floats ([blocks][257]). */
+ * floats ([blocks][257]).  d_gconf NULL: points_conf is frozen, the K-blend's d conf is not
+ * computed; everything else as with it. */
 int sgn_train_row_head(const sgn_point_tables *pt, const sgn_query_out *q, int32_t K, const int32_t *d_row_off,
                        const int32_t *d_counts, float *d_z4_delta4, const float *d_dfs, const float *d_dfeat,
                        const float *d_rw, const float *d_wa, const float *d_ba, float *d_gconf, uint32_t *d_amax,
                        float *d_part, sgn_stream_t stream);
 /* Point gradients of the rows (atomic adds, like the reference's index_add): d_dx0 [rows][224] =
- * d loss / d [emb | PE(emb)] -> points_embeding; d_dext [rows][8] -> points_color, points_dir. */
+ * d loss / d [emb | PE(emb)] -> points_embeding; d_dext [rows][8] -> points_color, points_dir.
+ * grads->conf is not read.  NULL grads->embedding / color / dir: frozen tensors, no lane works on
+ * them (d_dx0 may then be NULL with embedding, d_dext with both colour and dir); all three NULL
+ * returns 0 without a launch and writes nothing. */
 int sgn_train_row_tail(const sgn_point_tables *pt, const sgn_query_out *q, int32_t K, const int32_t *d_row_off,
                        const int32_t *d_counts, const float *d_dx0, const float *d_dext, const sgn_point_grads *grads,
                        sgn_stream_t stream);
@@ -731,7 +741,9 @@ size_t sgn_loss_workspace_bytes(int64_t R, int32_t SR);
  * float[8] (device): ray_masked_coarse_raycolor, conf_coefficient (zero-one), ray_miss_coarse_raycolor,
  * coarse_raycolor, then the gradient scales; d_dfeat float4[S] = d total / d feat of every sample of
  * the rays (written); d_dconf float[N] += d total / d conf (atomics).  total = d_losses[0] + 3e-6 +
- * zero_one_weight * d_losses[1].  No host synchronisation. */
+ * zero_one_weight * d_losses[1].  No host synchronisation.  d_dconf NULL: points_conf is frozen --
+ * the zero-one term is still computed and reported (d_losses[1]), only its gradients (point 0's
+ * empty-slot term included) are skipped. */
 int sgn_loss_train(const sgn_loss_params *lp, const float *d_campos, const float *d_camrotc2w, int64_t R,
                    const sgn_query_out *q, const float *d_feat, const float *d_gt, const float *d_conf,
                    float *d_out_rgb, int8_t *d_out_mask, float *d_losses, float *d_dfeat, float *d_dconf,

@@ -139,8 +139,11 @@ __host__ __device__ constexpr uint32_t prod_off(int I, int ks, int t, bool sg = 
 template <int I, bool SG = false>
 __host__ __device__ constexpr int prod_m(int ks, int t) { return I < 2 ? ks * prod_nt(I, SG) + t : t * 16 + ks; }
 
+// par: the tile's slot parity -- product I sits in slot (I & 1) ^ par.  0 wherever a tile runs an even
+// number of products (every tile then starts on slot 0); with the embedding frozen a tile runs
+// n_prod - 3 of them, an odd number, and the parity alternates from tile to tile
 template <int I, bool SG = false>
-__device__ __forceinline__ void prod_dma(char *lds, const WBlob &wb, const WBlob &tb, int w, int lane) {
+__device__ __forceinline__ void prod_dma(char *lds, const WBlob &wb, const WBlob &tb, int w, int lane, int par = 0) {
     constexpr int NT = prod_nt(I, SG), NF = 16 * NT;
     static_assert(NF % 4 == 0 && NF * (int)FRAG <= BWD_SLOT, "staging slot");
     const WBlob &src = I < 2 ? wb : tb;
@@ -149,7 +152,7 @@ __device__ __forceinline__ void prod_dma(char *lds, const WBlob &wb, const WBlob
     // VGPR lanes and read back with a readlane and hazard nops each)
     uint32_t wo = (uint32_t)w * (uint32_t)FRAG;
     asm volatile("" : "+s"(wo));
-    char *dst = lds + (I & 1) * BWD_SLOT + wo;
+    char *dst = lds + ((I & 1) ^ par) * BWD_SLOT + wo;
     const uint32_t src0 = (uint32_t)prod_off(I, 0, 0, SG) + wo;
 #pragma unroll
     for (int i = 0; i < NF / 4; ++i)
@@ -194,21 +197,24 @@ __device__ __forceinline__ void mask_dma(char *mr, const Tile &t, int k0) {
 // acc[t] (+)= sum_ks W_I(t, ks) * in[ks].  VM: boundary allowance (the stores of product I - 1's
 // epilogue); mask: the tile whose fragments k0 .. k0 + 7 product I's epilogue reads from the
 // region; `more`: the workgroup has another tile (the last product's successor is the next tile's
-// product 0)
-template <int I, int NT, bool SG, int VM>
+// product 0); LAST: product I is the tile's last although I + 1 < n_prod (the embedding is frozen: the
+// W0^T products are not run), its successor the next tile's product 0 in the other parity's slot
+template <int I, int NT, bool SG, int VM, bool LAST = false>
 __device__ __forceinline__ void prod_mul(char *lds, const WBlob &wb, const WBlob &tb, const h8 (&in)[16],
                                          f32x16 (&acc)[NT], int w, int lane, bool more,
-                                         const Tile *mask = nullptr, int k0 = 0) {
+                                         const Tile *mask = nullptr, int k0 = 0, int par = 0) {
     static_assert(NT == prod_nt(I, SG), "product width");
     boundary<VM>();
     if (mask) mask_dma(lds + BWD_LDS + w * MRW, *mask, k0);
     asm volatile("" ::: "memory");  // the masks' pieces stay older than the weights' (mask_wait counts)
-    if constexpr (I + 1 < n_prod(SG)) prod_dma<I + 1, SG>(lds, wb, tb, w, lane);
-    else if (more) prod_dma<0, SG>(lds, wb, tb, w, lane);
+    if constexpr (LAST) {
+        if (more) prod_dma<0, SG>(lds, wb, tb, w, lane, par ^ 1);
+    } else if constexpr (I + 1 < n_prod(SG)) prod_dma<I + 1, SG>(lds, wb, tb, w, lane, par);
+    else if (more) prod_dma<0, SG>(lds, wb, tb, w, lane, par);
     asm volatile("" ::: "memory");  // and the epilogue's stores younger than both (boundary counts)
     // opaque per product: hipcc hoisted every fragment's address out of the tile loop into its own
     // VGPR (64 of them); one base VGPR + the read's 16-bit immediate offset instead
-    uint32_t voff = (uint32_t)((I & 1) * BWD_SLOT + lane * 16);
+    uint32_t voff = (uint32_t)(((I & 1) ^ par) * BWD_SLOT + lane * 16);
     asm volatile("" : "+v"(voff));
     const char *sl = lds + voff;
     // fragment n = ks * NT + t read PF ahead of its MFMA: one read in flight per MFMA left the MFMAs
@@ -232,13 +238,13 @@ __device__ __forceinline__ void prod_mul(char *lds, const WBlob &wb, const WBlob
 }
 
 // acc[t] = sum_ks T[t0 + t][ks] * in[ks] for the NT row tiles of transposed product I
-template <int I, int NT, bool SG, int VM>
+template <int I, int NT, bool SG, int VM, bool LAST = false>
 __device__ __forceinline__ void tmul(char *lds, const WBlob &wb, const WBlob &tb, const h8 (&in)[16],
                                      f32x16 (&acc)[NT], int w, int lane, bool more, const Tile *mask = nullptr,
-                                     int k0 = 0) {
+                                     int k0 = 0, int par = 0) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = f32x16{};
-    prod_mul<I, NT, SG, VM>(lds, wb, tb, in, acc, w, lane, more, mask, k0);
+    prod_mul<I, NT, SG, VM, LAST>(lds, wb, tb, in, acc, w, lane, more, mask, k0, par);
 }
 
 // product I's epilogue reads its masks: the DMA pieces issued after them (product I + 1's
@@ -247,6 +253,13 @@ template <int I, bool SG>
 __device__ __forceinline__ void mask_wait() {
     static_assert(I + 1 < n_prod(SG), "a masked product has a successor in the tile");
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * prod_nt(I + 1, SG)) : "memory");
+}
+
+// the tile's last product (LAST): the pieces issued after its masks are the next tile's product 0 (16)
+// when the workgroup has another tile, none otherwise
+__device__ __forceinline__ void mask_wait_last(bool more) {
+    if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * prod_nt(0)) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // d feat[c] contribution of layer-0 local channel C (mlp_layout.h l0 order): PE(feat) chain rule
@@ -280,8 +293,12 @@ __device__ __forceinline__ void masked_epilogue(const char *lds, int w, const f3
         }
 }
 
-template <bool SG>
+// EMB: points_embeding is trained; frozen, block1.0's input-gradient products (W0^T delta1) and the
+// PE(feat) chain are not run at all.  SEL: the colour / dir / conf gradients are issued where their
+// pointer (a wave-uniform kernel argument) is non-NULL; <SG, true, false> is the all-trained kernel.
+template <bool SG, bool EMB = true, bool SEL = false>
 __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
+    static_assert(EMB || SEL, "a frozen embedding comes with the selectable variant");
     constexpr int IW1 = prod_w1(SG), IW0 = prod_w0(SG);
     __shared__ __attribute__((aligned(16))) char lds[BWD_LDS_ALL];
     const AggArgs &a = b.a;
@@ -296,6 +313,7 @@ __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
     const float scale = *b.scale, inv = 1.f / scale;
     const int end = b.n_items;
     if (blockIdx.x * 16 < end) prod_dma<0, SG>(lds, wb, tb, w, lane);  // stream prologue
+    int par = 0;  // the tile's slot parity (prod_dma): constant 0 while the embedding is trained
     // trip count uniform over the workgroup (its waves meet at the staging barriers); rows past
     // the end are masked (ok = false) and out of the tiles' range
     for (int bbase = blockIdx.x * 16; bbase < end; bbase += gridDim.x * 16) {
@@ -306,6 +324,8 @@ __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
         const int nrow = min(max(end - base, 0), 4) * 8;
         // this wave's d f_s rows and the fp32 constants -> its region (landed at product 0's boundary;
         // the region's last readers, the previous tile's block1.2 epilogue, are past 3 boundaries)
+        // (embedding frozen: the last readers are the previous tile's last instructions -- their reads done)
+        if constexpr (!EMB) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         {
             const __amdgpu_buffer_rsrc_t rd = rsrc_u(b.dfs + (int64_t)base * HID, nrow / 8 * HID * 4);
 #pragma unroll
@@ -332,8 +352,8 @@ __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
             for (int s = 0; s < 16; ++s) x3[s] = t3.load(s);
 #pragma unroll
             for (int t = 0; t < 8; ++t) acc[t] = f32x16{};
-            prod_mul<0, 4, SG, 0>(lds, wb, tb, x3, *(f32x16(*)[4])&acc[0], w, lane, more);
-            prod_mul<1, 4, SG, 0>(lds, wb, tb, x3, *(f32x16(*)[4])&acc[4], w, lane, more);
+            prod_mul<0, 4, SG, 0>(lds, wb, tb, x3, *(f32x16(*)[4])&acc[0], w, lane, more, nullptr, 0, par);
+            prod_mul<1, 4, SG, 0>(lds, wb, tb, x3, *(f32x16(*)[4])&acc[4], w, lane, more, nullptr, 0, par);
         }
         // ---- pass 1: h4, alpha logit, <h4, d f_s> ------------------------------------------
         const float *dfl = (const float *)(mr + q * MR_DFS);
@@ -399,10 +419,10 @@ __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
         {
             const Tile td3 = tile_of(b.d3, 256, row0, nrow, lane);
             f32x16 ac[4];
-            tmul<2, 4, SG, 33>(lds, wb, tb, dl, ac, w, lane, more, &t3, 0);
+            tmul<2, 4, SG, 33>(lds, wb, tb, dl, ac, w, lane, more, &t3, 0, par);
             mask_wait<2, SG>();
             masked_epilogue<0>(lds, w, ac, dn, td3, lane);
-            tmul<3, 4, SG, 8>(lds, wb, tb, dl, ac, w, lane, more, &t3, 8);
+            tmul<3, 4, SG, 8>(lds, wb, tb, dl, ac, w, lane, more, &t3, 8, par);
             mask_wait<3, SG>();
             masked_epilogue<1>(lds, w, ac, dn, td3, lane);
         }
@@ -412,28 +432,38 @@ __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
             const Tile t2 = tile_of(b.sh2, KS_L2 * 16, row0, nrow, lane);
             const Tile td2 = tile_of(SG ? b.db : b.d2, 256, row0, nrow, lane);
             f32x16 ac[4];
-            tmul<4, 4, SG, 8>(lds, wb, tb, dn, ac, w, lane, more, &t2, 0);
+            tmul<4, 4, SG, 8>(lds, wb, tb, dn, ac, w, lane, more, &t2, 0, par);
             mask_wait<4, SG>();
             masked_epilogue<0>(lds, w, ac, dl, td2, lane);
-            tmul<5, 4, SG, 8>(lds, wb, tb, dn, ac, w, lane, more, &t2, 8);
+            tmul<5, 4, SG, 8>(lds, wb, tb, dn, ac, w, lane, more, &t2, 8, par);
             mask_wait<5, SG>();
             masked_epilogue<1>(lds, w, ac, dl, td2, lane);
         }
         {
             f32x16 ae[1];
-            tmul<6, 1, SG, 8>(lds, wb, tb, dn, ae, w, lane, more);
+            tmul<6, 1, SG, 8>(lds, wb, tb, dn, ae, w, lane, more, nullptr, 0, par);
             // tile 8 = inputs 256..262: half 0 regs 0..3 -> colour 0..2, (dir - v)_0;
             // half 1 regs 0..2 -> (dir - v)_1, (dir - v)_2, <dir, v>   (:639-652)
             const float o0 = __shfl_xor(ae[0][0], 32), o1 = __shfl_xor(ae[0][1], 32), o2 = __shfl_xor(ae[0][2], 32);
             if (ok && ri.pid >= 0 && h == 0) {
                 const float ddiff[3] = {ae[0][3], o0, o1};
                 const int64_t pb = (int64_t)ri.pid * 3;
+                if constexpr (!SEL) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    atomicAdd(b.g_color + pb + c, ae[0][c] * inv);
-                    atomicAdd(b.g_dir + pb + c, fmaf(o2, vr[c], ddiff[c]) * inv);
+                    for (int c = 0; c < 3; ++c) {
+                        atomicAdd(b.g_color + pb + c, ae[0][c] * inv);
+                        atomicAdd(b.g_dir + pb + c, fmaf(o2, vr[c], ddiff[c]) * inv);
+                    }
+                    atomicAdd(b.g_conf + ri.pid, dwgt * ri.wn * inv);  // straight-through clamp (:863-865)
+                } else {  // the trained tensors' atomics only (NULL: frozen)
+                    if (b.g_color)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) atomicAdd(b.g_color + pb + c, ae[0][c] * inv);
+                    if (b.g_dir)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) atomicAdd(b.g_dir + pb + c, fmaf(o2, vr[c], ddiff[c]) * inv);
+                    if (b.g_conf) atomicAdd(b.g_conf + ri.pid, dwgt * ri.wn * inv);
                 }
-                atomicAdd(b.g_conf + ri.pid, dwgt * ri.wn * inv);  // straight-through clamp (:863-865)
             }
         }
         // (the atomics are conditional: the next boundary drains vmcnt)
@@ -442,10 +472,10 @@ __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
             const Tile tb2 = tile_of(b.sh2b, 256, row0, nrow, lane);
             const Tile td2 = tile_of(b.d2, 256, row0, nrow, lane);
             f32x16 ac[4];
-            tmul<7, 4, SG, 0>(lds, wb, tb, dl, ac, w, lane, more, &tb2, 0);
+            tmul<7, 4, SG, 0>(lds, wb, tb, dl, ac, w, lane, more, &tb2, 0, par);
             mask_wait<7, SG>();
             masked_epilogue<0>(lds, w, ac, dn, td2, lane);
-            tmul<8, 4, SG, 8>(lds, wb, tb, dl, ac, w, lane, more, &tb2, 8);
+            tmul<8, 4, SG, 8>(lds, wb, tb, dl, ac, w, lane, more, &tb2, 8, par);
             mask_wait<8, SG>();
             masked_epilogue<1>(lds, w, ac, dn, td2, lane);
 #pragma unroll
@@ -456,12 +486,17 @@ __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
             const Tile t1 = tile_of(b.sh1, 256, row0, nrow, lane);
             const Tile td1 = tile_of(b.d1, 256, row0, nrow, lane);
             f32x16 ac[4];
-            tmul<IW1, 4, SG, SG ? 8 : 0>(lds, wb, tb, dl, ac, w, lane, more, &t1, 0);
+            tmul<IW1, 4, SG, SG ? 8 : 0>(lds, wb, tb, dl, ac, w, lane, more, &t1, 0, par);
             mask_wait<IW1, SG>();
             masked_epilogue<0>(lds, w, ac, dn, td1, lane);
-            tmul<IW1 + 1, 4, SG, 8>(lds, wb, tb, dl, ac, w, lane, more, &t1, 8);
-            mask_wait<IW1 + 1, SG>();
+            tmul<IW1 + 1, 4, SG, 8, !EMB>(lds, wb, tb, dl, ac, w, lane, more, &t1, 8, par);
+            if constexpr (EMB) mask_wait<IW1 + 1, SG>();
+            else mask_wait_last(more);
             masked_epilogue<1>(lds, w, ac, dn, td1, lane);
+        }
+        if constexpr (!EMB) {  // delta1 is stored for block1.0's weight gradient; d x0 has no reader
+            par ^= 1;
+            continue;
         }
         // ---- block1.0 backward: d x0 = W0^T delta1 -> d feat through PE(feat) --------------
         float dfe[16];
@@ -470,7 +505,7 @@ __global__ __launch_bounds__(BWD_TPB) void k_agg_bwd(BwdArgs b) {
         static_for<3>([&](auto pp) {
             constexpr int P = decltype(pp)::value;
             f32x16 ac[3];
-            tmul<IW0 + P, 3, SG, P == 0 ? 8 : 0>(lds, wb, tb, dn, ac, w, lane, more);
+            tmul<IW0 + P, 3, SG, P == 0 ? 8 : 0>(lds, wb, tb, dn, ac, w, lane, more, nullptr, 0, par);
             static_for<3>([&](auto ttc) {
                 constexpr int T = 3 * P + decltype(ttc)::value;
                 static_for<16>([&](auto rr) {
@@ -607,7 +642,6 @@ int sgn_aggregate_backward(int32_t bpnet_layers, int32_t bpnet_dim, const sgn_po
     if (n_items == 0) return 0;
     SGN_REQUIRE(d_dfs && d_dalpha && saved->h1 && saved->h2 && saved->h3, "null saved/input tensors");
     SGN_REQUIRE(deltas->d1 && deltas->d2 && deltas->d3 && deltas->d4 && deltas->h4 && deltas->dza, "null delta outputs");
-    SGN_REQUIRE(grads->embedding && grads->color && grads->dir && grads->conf, "null gradient outputs");
     BwdArgs b{};
     fill_agg_args(b.a, pt, q, K);
     b.a.blob = d_packed; b.a.blob_bytes = mlp::total_bytes_sg(ksb);
@@ -624,7 +658,13 @@ int sgn_aggregate_backward(int32_t bpnet_layers, int32_t bpnet_dim, const sgn_po
     b.n_items = n_items;
     const int64_t waves = ((int64_t)n_items + 3) / 4;
     const int64_t blocks = (waves + 3) / 4;
-    auto kern = ksb == 0 ? k_agg_bwd<false> : k_agg_bwd<true>;
+    // a NULL member of grads is a frozen tensor.  All four trained: the stock kernel; otherwise the
+    // selectable one, without block1.0's input-gradient products when the embedding is frozen.  The
+    // deltas are written either way (the weight gradients read them).
+    const bool all = grads->embedding && grads->color && grads->dir && grads->conf;
+    auto kern = all ? (ksb == 0 ? k_agg_bwd<false> : k_agg_bwd<true>)
+                : grads->embedding ? (ksb == 0 ? k_agg_bwd<false, true, true> : k_agg_bwd<true, true, true>)
+                                   : (ksb == 0 ? k_agg_bwd<false, false, true> : k_agg_bwd<true, false, true>);
     hipLaunchKernelGGL(kern, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(BWD_TPB), 0,
                        as_stream(stream), b);
     SGN_CHECK_HIP(hipGetLastError());

@@ -209,6 +209,9 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_reduce(LossArgs a, int nblock
     }
 }
 
+// CONF: points_conf is trained (dconf non-NULL); frozen, the zero-one term is still in the loss
+// (k_loss_fwd) and only its gradient -- the loop below, point 0's empty-slot term included -- goes
+template <bool CONF>
 __global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(LossArgs a) {
     const int64_t r = ((int64_t)blockIdx.x * LOSS_TPB + threadIdx.x) / LPR;
     const int sub = threadIdx.x % LPR;
@@ -250,6 +253,7 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(LossArgs a) {
             U += gc * w;
         }
     }
+    if constexpr (!CONF) return;
     // zero-one gradients, neighbour k = sub, sub + 8, ..; the empty entries all read conf[0]
     const float gz = a.sums[5];
     float t0, d0;
@@ -288,7 +292,7 @@ int sgn_loss_train(const sgn_loss_params *lp, const float *d_campos, const float
                    void *d_workspace, size_t workspace_bytes, sgn_stream_t stream) {
     using namespace sgn;
     SGN_REQUIRE(lp && q && d_campos && d_camrotc2w && d_feat && d_gt && d_conf && d_out_rgb && d_out_mask &&
-                    d_losses && d_dfeat && d_dconf && d_workspace,
+                    d_losses && d_dfeat && d_workspace,
                 "null argument");
     SGN_REQUIRE(lp->SR > 0 && lp->K > 0, "SR and K must be positive");
     SGN_REQUIRE(R >= 0, "R must be non-negative");
@@ -315,7 +319,7 @@ int sgn_loss_train(const sgn_loss_params *lp, const float *d_campos, const float
     }
     hipLaunchKernelGGL(k_loss_fwd, dim3((unsigned)nb), dim3(LOSS_TPB), 0, st, a);
     hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(LOSS_TPB), 0, st, a, (int)nb);
-    hipLaunchKernelGGL(k_loss_bwd, dim3((unsigned)nb), dim3(LOSS_TPB), 0, st, a);
+    hipLaunchKernelGGL(d_dconf ? k_loss_bwd<true> : k_loss_bwd<false>, dim3((unsigned)nb), dim3(LOSS_TPB), 0, st, a);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
 }

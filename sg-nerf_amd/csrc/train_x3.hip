@@ -1143,6 +1143,8 @@ __device__ __forceinline__ float lane_value(float x, int l) {
 
 constexpr int MAX_K = 8;
 
+// CONF: points_conf is trained (g_conf non-NULL); frozen, the K-blend's d conf has nowhere to go
+template <bool CONF>
 __global__ __launch_bounds__(TPB) void k_row_head(RowArgs a, float *z4d4, const float *dfs, const float4 *dfeat,
                                                   const float2 *rw, const float *wa, const float *ba, float *g_conf,
                                                   uint32_t *amax, float *part) {
@@ -1203,9 +1205,10 @@ __global__ __launch_bounds__(TPB) void k_row_head(RowArgs a, float *z4d4, const 
             }
             gb += dza;
             *(f32x4 *)(z4d4 + (int64_t)(ro + k) * 256 + 4 * lane) = d;
-            if (lane == k) gc = dw * wnk;
+            if (CONF && lane == k) gc = dw * wnk;
         }
-        if (lane < nnb) atomicAdd(g_conf + a.pidx[(int64_t)s * a.K + lane], gc);
+        if constexpr (CONF)
+            if (lane < nnb) atomicAdd(g_conf + a.pidx[(int64_t)s * a.K + lane], gc);
     }
     *(f32x4 *)&sh[wl][4 * lane] = gw;
     if (lane == 0) sh[wl][256] = gb;
@@ -1226,9 +1229,16 @@ __global__ __launch_bounds__(TPB) void k_row_head(RowArgs a, float *z4d4, const 
 // tasks per row: 32 embedding channels, then colour (3) and dir (3); the item's rows x tasks are
 // one flat list over the wave's lanes
 constexpr int TAIL_TASKS = 38;
-
+// TR: the trained tensors (bit 0 embedding, 1 colour, 2 dir; a frozen tensor's gradient is NULL).  The
+// task list holds the trained channels only -- 32 TR.0 + 3 TR.1 + 3 TR.2 lanes per row -- so no lane
+// is spent on a frozen tensor and a frozen embedding evaluates no sincos chain; each task ends in the
+// one atomic.  TR = 7 is the list above.
+template <int TR>
 __global__ __launch_bounds__(TPB) void k_row_tail(RowArgs a, const float *dx0, const float *dext, float *g_emb,
                                                   float *g_color, float *g_dir) {
+    constexpr int NE = TR & 1 ? 32 : 0, NC = TR & 2 ? 3 : 0, ND = TR & 4 ? 3 : 0;
+    constexpr int TASKS = NE + NC + ND;
+    static_assert(TASKS > 0 && (TR != 7 || TASKS == TAIL_TASKS), "at least one trained tensor");
     const int lane = threadIdx.x & 63;
     const int wv = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6), nw = gridDim.x * (TPB / 64);
     const int n = n_items(a);
@@ -1236,33 +1246,64 @@ __global__ __launch_bounds__(TPB) void k_row_tail(RowArgs a, const float *dx0, c
         const int s = a.work[it];
         const int nnb = a.samp_nnb[s], ro = a.row_off[s];
         const int ray = a.samp_ray[s];
-        const int ntask = nnb * TAIL_TASKS;
+        const int ntask = nnb * TASKS;
         for (int t = lane; t < ntask; t += 64) {
-            const int k = t / TAIL_TASKS, c = t - k * TAIL_TASKS;
+            const int k = t / TASKS, c = t - k * TASKS;
             const int64_t j = ro + k;
             const int pid = a.pidx[(int64_t)s * a.K + k];
-            if (c < 32) {
-                const float *g = dx0 + j * 224;
-                const float e = a.emb[(int64_t)pid * 32 + c];
-                float de = g[c];
+            if constexpr (TR == 7) {
+                if (c < 32) {
+                    const float *g = dx0 + j * 224;
+                    const float e = a.emb[(int64_t)pid * 32 + c];
+                    float de = g[c];
 #pragma unroll
-                for (int f = 0; f < 3; ++f) {
-                    const float sc = (float)(1 << f);
-                    float sn, cs;
-                    sincos_acc(e * sc, sn, cs);
-                    const int col = 32 + 2 * (3 * c + f);
-                    de += g[col] * cs * sc - g[col + 1] * sn * sc;
-                }
-                atomicAdd(g_emb + (int64_t)pid * 32 + c, de);
-            } else {
-                const int u = c - 32;
-                const float *g = dext + j * 8;
-                if (u < 3) {
-                    atomicAdd(g_color + (int64_t)pid * 3 + u, g[u]);
+                    for (int f = 0; f < 3; ++f) {
+                        const float sc = (float)(1 << f);
+                        float sn, cs;
+                        sincos_acc(e * sc, sn, cs);
+                        const int col = 32 + 2 * (3 * c + f);
+                        de += g[col] * cs * sc - g[col + 1] * sn * sc;
+                    }
+                    atomicAdd(g_emb + (int64_t)pid * 32 + c, de);
                 } else {
-                    const float v = a.raydir[(int64_t)ray * 3 + u - 3];
-                    atomicAdd(g_dir + (int64_t)pid * 3 + u - 3, g[u] + g[6] * v);
+                    const int u = c - 32;
+                    const float *g = dext + j * 8;
+                    if (u < 3) {
+                        atomicAdd(g_color + (int64_t)pid * 3 + u, g[u]);
+                    } else {
+                        const float v = a.raydir[(int64_t)ray * 3 + u - 3];
+                        atomicAdd(g_dir + (int64_t)pid * 3 + u - 3, g[u] + g[6] * v);
+                    }
                 }
+            } else {
+                float *dst;
+                float val;
+                if (NE && c < NE) {
+                    const float *g = dx0 + j * 224;
+                    const float e = a.emb[(int64_t)pid * 32 + c];
+                    val = g[c];
+#pragma unroll
+                    for (int f = 0; f < 3; ++f) {
+                        const float sc = (float)(1 << f);
+                        float sn, cs;
+                        sincos_acc(e * sc, sn, cs);
+                        const int col = 32 + 2 * (3 * c + f);
+                        val += g[col] * cs * sc - g[col + 1] * sn * sc;
+                    }
+                    dst = g_emb + (int64_t)pid * 32 + c;
+                } else {
+                    const int u = c - NE;   // colour channels first, then dir
+                    const float *g = dext + j * 8;
+                    if (NC && u < NC) {
+                        val = g[u];
+                        dst = g_color + (int64_t)pid * 3 + u;
+                    } else {
+                        const int d = u - NC;
+                        val = g[3 + d] + g[6] * a.raydir[(int64_t)ray * 3 + d];
+                        dst = g_dir + (int64_t)pid * 3 + d;
+                    }
+                }
+                atomicAdd(dst, val);
             }
         }
     }
@@ -1610,14 +1651,16 @@ int sgn_train_row_head(const sgn_point_tables *pt, const sgn_query_out *q, int32
                        float *d_part, sgn_stream_t stream) {
     using namespace sgn;
     using namespace sgn::tx;
-    SGN_REQUIRE(pt && q && d_row_off && d_counts && d_z4_delta4 && d_dfs && d_dfeat && d_rw && d_wa && d_ba && d_gconf &&
-                    d_amax && d_part,
+    SGN_REQUIRE(pt && q && d_row_off && d_counts && d_z4_delta4 && d_dfs && d_dfeat && d_rw && d_wa && d_ba && d_amax &&
+                    d_part,
                 "null argument");
     SGN_REQUIRE(K >= 1 && K <= 8, "K = 1 .. 8");
     SGN_REQUIRE_NO_ROT(pt);
     const RowArgs a = row_args(pt, q, K, d_row_off, d_counts);
-    hipLaunchKernelGGL(k_row_head, dim3(ROW_HEAD_BLOCKS), dim3(TPB), 0, as_stream(stream), a, d_z4_delta4, d_dfs,
-                       (const float4 *)d_dfeat, (const float2 *)d_rw, d_wa, d_ba, d_gconf, d_amax, d_part);
+    // d_gconf NULL: points_conf is frozen
+    hipLaunchKernelGGL(d_gconf ? k_row_head<true> : k_row_head<false>, dim3(ROW_HEAD_BLOCKS), dim3(TPB), 0,
+                       as_stream(stream), a, d_z4_delta4, d_dfs, (const float4 *)d_dfeat, (const float2 *)d_rw, d_wa, d_ba,
+                       d_gconf, d_amax, d_part);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1627,12 +1670,17 @@ int sgn_train_row_tail(const sgn_point_tables *pt, const sgn_query_out *q, int32
                        sgn_stream_t stream) {
     using namespace sgn;
     using namespace sgn::tx;
-    SGN_REQUIRE(pt && q && d_row_off && d_counts && d_dx0 && d_dext && grads, "null argument");
-    SGN_REQUIRE(grads->embedding && grads->color && grads->dir, "null gradient outputs");
+    SGN_REQUIRE(pt && q && d_row_off && d_counts && grads, "null argument");
+    // a NULL member is a frozen tensor; d_dx0 is read for the embedding only, d_dext for colour / dir
+    const int tr = (grads->embedding ? 1 : 0) | (grads->color ? 2 : 0) | (grads->dir ? 4 : 0);
+    SGN_REQUIRE((!(tr & 1) || d_dx0) && (!(tr & 6) || d_dext), "null input gradient of a trained tensor");
     SGN_REQUIRE(K >= 1 && K <= 8, "K = 1 .. 8");
     SGN_REQUIRE_NO_ROT(pt);
+    if (tr == 0) return 0;   // nothing trained: no launch
     const RowArgs a = row_args(pt, q, K, d_row_off, d_counts);
-    hipLaunchKernelGGL(k_row_tail, dim3(ROW_GRID), dim3(TPB), 0, as_stream(stream), a, d_dx0, d_dext, grads->embedding,
+    static constexpr decltype(&k_row_tail<7>) kern[8] = {nullptr,       k_row_tail<1>, k_row_tail<2>, k_row_tail<3>,
+                                                         k_row_tail<4>, k_row_tail<5>, k_row_tail<6>, k_row_tail<7>};
+    hipLaunchKernelGGL(kern[tr], dim3(ROW_GRID), dim3(TPB), 0, as_stream(stream), a, d_dx0, d_dext, grads->embedding,
                        grads->color, grads->dir);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;

@@ -30,7 +30,8 @@ class _HipLoss(torch.autograd.Function):
     def backward(ctx, g_losses, g_full, g_mask):
         dfeat, dconf = ctx.saved_tensors
         # losses[0] = ray_masked_coarse_raycolor (d/d feat in dfeat), losses[1] = zero-one (d/d conf in dconf)
-        return dfeat * g_losses[0], dconf * g_losses[1], None
+        # (dconf None: points_conf is frozen, the kernel skipped its zero-one gradients)
+        return dfeat * g_losses[0], None if dconf is None else dconf * g_losses[1], None
 
 
 class LossStage:
@@ -79,13 +80,13 @@ class LossStage:
             full = torch.empty(R, 3, dtype=torch.float32, device=dev)
             mask = torch.empty(R, dtype=torch.int8, device=dev)
             dfeat = torch.zeros_like(feat_t)   # entries past the rays' samples (capacity padding) stay 0
-            dconf = torch.zeros(n_points, dtype=torch.float32, device=dev)
+            dconf = torch.zeros(n_points, dtype=torch.float32, device=dev) if conf_t.requires_grad else None
             _lib.check(_lib.lib().sgn_loss_train(ctypes.byref(lp), _lib.ptr(campos), _lib.ptr(rot), R,
                                                  ctypes.byref(q_abi), _lib.ptr(feat_t.detach()), _lib.ptr(gt),
                                                  _lib.ptr(conf_t.detach()), _lib.ptr(full), _lib.ptr(mask),
                                                  _lib.ptr(losses), _lib.ptr(dfeat), _lib.ptr(dconf), _lib.ptr(ws),
                                                  ws.numel(), _lib.stream_handle()), "sgn_loss_train")
-            return losses, full, mask, dfeat, dconf.view(conf_t.shape)
+            return losses, full, mask, dfeat, None if dconf is None else dconf.view(conf_t.shape)
 
         losses, full, mask = _HipLoss.apply(feat, conf, run)
         l_col, l_zo = losses[0], losses[1]

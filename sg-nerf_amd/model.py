@@ -181,7 +181,11 @@ class HipPointsVolumetricModel:
 
     # -- training (mvs_points_volumetric_model.py:47-141, base_model.py:138-160) -----------------
     def setup_optimizer(self, opt):
-        """Two Adam groups, aggregator (lr) and neural points (plr), as the reference builds them."""
+        """Two Adam groups, aggregator (lr) and neural points (plr), as the reference builds them.  The
+        point group holds the tensors opt.feat_grad / color_grad / dir_grad / conf_grad train (self.opts,
+        read from opt at initialize(); neural_points.py:410-416): a frozen tensor keeps its values through
+        every step, prune / grow rebuild and checkpoint, and neural_points.points_* stay views of the
+        trainer's tensors either way."""
         from .train import PointParams
         from .train_hip import HipTrainer
         if self.neural_points is None or self.net_ray_marching is None:

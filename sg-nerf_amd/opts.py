@@ -63,6 +63,15 @@ class HotPathOpts:
     point_color_mode: str = "1"
     point_dir_mode: str = "1"
     point_conf_mode: str = "1"
+    # which neural-point tensors train (neural_points.py:410-416, again after prune / grow :527-536,
+    # :553-560): any non-zero value means trained (the reference tests `> 0`), a frozen tensor gets no
+    # gradient and no Adam moments.  The defaults are scene241.sh:13-16 (all four trained), not the
+    # reference's argparse default dir_grad 0: a driver's opt always carries the real value (from_opt).
+    feat_grad: int = 1
+    color_grad: int = 1
+    dir_grad: int = 1
+    conf_grad: int = 1
+    xyz_grad: int = 0          # positions feed the grid and the query, which carry no gradient here
     # ray marching (neural_points_volumetric_model.py)
     raydist_mode_unit: int = 1
     which_tonemap_func: str = "off"
@@ -83,6 +92,13 @@ class HotPathOpts:
         if self.shading_feature_mlp_layer2_bpnet == 0:
             return 0, 0
         return 1, (96 if self.predict_semantic == 1 else 0)
+
+    @property
+    def trained_points(self):
+        """The trained point tensors' names, in the point Adam group's order."""
+        sw = (("points_embeding", self.feat_grad), ("points_color", self.color_grad), ("points_dir", self.dir_grad),
+              ("points_conf", self.conf_grad))
+        return tuple(name for name, v in sw if v)
 
     @classmethod
     def from_opt(cls, opt, **overrides):
@@ -133,6 +149,8 @@ class HotPathOpts:
             bad.append("precision must be 'f32' (reference arithmetic) or 'f16'")
         if self.inverse != 0:
             bad.append("inverse (disparity) ray generation is not implemented")
+        if self.xyz_grad:
+            bad.append("xyz_grad must be 0 (point positions feed the grid and the query, which carry no gradient)")
         if bad:
             raise NotImplementedError("; ".join(bad))
         return self

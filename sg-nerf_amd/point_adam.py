@@ -7,13 +7,58 @@ import torch
 from . import _lib
 
 
+def _check_point_tensors(names, state_dict):
+    """A state written under other grad switches (another set of trained point tensors) is refused."""
+    if names is None:
+        return
+    groups = state_dict.get("param_groups") or [{}]
+    theirs = groups[0].get("point_tensors")
+    if theirs is None:   # written before the switches existed: every tensor of its group trained
+        if len(groups[0].get("params", ())) == len(names):
+            return
+        theirs = "%d unnamed tensors" % len(groups[0].get("params", ()))
+    elif tuple(theirs) == tuple(names):
+        return
+    raise ValueError(f"point Adam state was written with trained tensors {theirs}, this optimizer trains "
+                     f"{list(names)}: the feat_grad / color_grad / dir_grad / conf_grad switches differ")
+
+
+class NoPointAdam:
+    """The point group with every tensor frozen (feat_grad = color_grad = dir_grad = conf_grad = 0):
+    nothing to step, no launch, an empty state that round-trips and refuses another switch set's."""
+    rows_mode = False
+    zero_grad_in_step = True
+    names = ()
+
+    def __init__(self, lr):
+        self.param_groups = [{"params": [], "lr": lr, "point_tensors": []}]
+        self.state = {}
+
+    def step(self, closure=None):
+        return None
+
+    def zero_grad(self, set_to_none=True):
+        pass
+
+    def flush(self):
+        pass
+
+    def state_dict(self):
+        return {"state": {}, "param_groups": [dict(self.param_groups[0], params=[])]}
+
+    def load_state_dict(self, state_dict):
+        _check_point_tensors(self.names, state_dict)
+        self.param_groups[0]["lr"] = state_dict["param_groups"][0].get("lr", self.param_groups[0]["lr"])
+
+
 class PointAdam(torch.optim.Adam):
     """torch.optim.Adam (same param_groups, state keys and state_dict) whose step is one
     sgn_adam_step_multi launch per parameter group; with zero_grad the launch also clears the
     gradients, so the next step skips their fill pass.  For the dense ~47 M-element point group
     and the MLP's flat parameter."""
 
-    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, zero_grad=True, rows=False, flush_every=256):
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, zero_grad=True, rows=False, flush_every=256,
+                 names=None, row0=True):
         """rows: row-sparse exact mode (one group of <= 4 tensors sharing their first dimension, the
         points; sgn_adam_rows).  A row is brought forward only when something reads it, replaying the
         zero-gradient steps it missed, so it equals the dense update bit for bit whenever read.  The
@@ -22,8 +67,19 @@ class PointAdam(torch.optim.Adam):
         one pass; flush() (state_dict, the model's renders; every flush_every steps, which bounds the
         replay) brings every row.  The narrow tensors' moments (widths <= 8, e.g. colour, dir, conf: 7
         floats a row) share one [N, 16] buffer, m in columns 0-7 and v in 8-15, and the state holds views
-        of it: a row's moments are one 64-byte access instead of six scattered 4-12 byte ones."""
+        of it: a row's moments are one 64-byte access instead of six scattered 4-12 byte ones.
+
+        names: the group's tensors by name -- the trained point tensors (opt.feat_grad / color_grad /
+        dir_grad / conf_grad; a frozen tensor is not in the group and has no moments).  They travel in
+        the state_dict, and a state written under other names is refused.  row0: bring row 0 forward with
+        every listed step (the empty neighbour slots read point 0's conf: needed while conf trains)."""
         super().__init__(params, lr=lr, betas=betas, eps=eps)
+        self.names = None if names is None else tuple(names)
+        if self.names is not None:
+            if len(self.names) != sum(len(g["params"]) for g in self.param_groups):
+                raise ValueError("PointAdam: one name per tensor")
+            self.param_groups[0]["point_tensors"] = list(self.names)
+        self.row0 = bool(row0)
         self.zero_grad_in_step = zero_grad
         self.rows_mode = rows
         if rows:
@@ -111,7 +167,7 @@ class PointAdam(torch.optim.Adam):
             n, arr(ps), arr([p.grad if apply else None for p in ps]), arr([self.state[p]["exp_avg"] for p in ps]),
             arr([self.state[p]["exp_avg_sq"] for p in ps]), self._width, self._mstride, self.n_rows,
             _lib.ptr(rows) if rows is not None else None, _lib.ptr(count) if count is not None else None,
-            int(count_is64), count_mul, n_max, 1,
+            int(count_is64), count_mul, n_max, int(self.row0),
             prev[0].data_ptr() + 16 if prev is not None else None, prev[0].data_ptr() if prev is not None else None,
             n2, _lib.ptr(self._last), _lib.ptr(self._claim), _lib.ptr(self._claim2), self._tag,
             _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(pb) if pb is not None else None,
@@ -166,6 +222,7 @@ class PointAdam(torch.optim.Adam):
         super().zero_grad(set_to_none)
 
     def load_state_dict(self, state_dict):
+        _check_point_tensors(self.names, state_dict)
         super().load_state_dict(state_dict)
         if self.rows_mode:   # the loaded tensors are a dense state: every row holds its step
             for i, p in enumerate(self.param_groups[0]["params"]):

@@ -425,6 +425,14 @@ class Trainer:
         self.mlp = ViewMLP(mlp_state).to(self.device)
         self.net_params = list(self.mlp.parameters())
         self.point_params = [points.points_embeding, points.points_color, points.points_dir, points.points_conf]
+        # opt.feat_grad / color_grad / dir_grad / conf_grad, the reference's way (neural_points.py:410-416):
+        # requires_grad off, the tensor still listed in the group (torch's Adam skips it: no gradient)
+        trained = getattr(opts, "trained_points", None)
+        for name in ("points_embeding", "points_color", "points_dir", "points_conf"):
+            p = getattr(points, name)
+            p.requires_grad_(trained is None or name in trained)
+            if not p.requires_grad:
+                p.grad = None
         self.opt_net = torch.optim.Adam(self.net_params, lr=lr, betas=(0.9, 0.999))
         self.opt_pts = torch.optim.Adam(self.point_params, lr=plr, betas=(0.9, 0.999))
         self.base_lr = (lr, plr)
@@ -466,10 +474,12 @@ class Trainer:
                                                        bg)
         total.backward()
         for p in self.point_params + self.net_params:
-            if p.grad is None:
+            if p.grad is None and p.requires_grad:
                 p.grad = torch.zeros_like(p)
         self.allreduce_grads(self.net_params)
-        _allreduce_point_rows([p.grad for p in self.point_params])
+        trained = [p.grad for p in self.point_params if p.requires_grad]
+        if trained:   # the sparse row exchange carries the trained tensors only
+            _allreduce_point_rows(trained)
         parts["total"] = total.detach()
         return parts, full.detach(), ray_mask
 

@@ -185,7 +185,8 @@ class F16Step:
         if not b.dp:
             self._cnt_host.copy_(q.counters[:2], non_blocking=True)
             self._cnt_event.record()
-        tr._adam_rows(q.pidx, q.counters, False, tr.opts.K)
+        if tr._adam_rows(q.pidx, q.counters, False, tr.opts.K) is None and not tr.point_params:
+            tr.touched_points(q)   # every point tensor frozen: no Adam launch, the OOB watch still sees the step
         # work that does not depend on the counts is queued before the step's one host sync, so the
         # GPU runs it while the host waits, and still has it queued when the host issues the rest
         self._blobs = tr.packer.pack(tr.mlp.flat)
@@ -246,9 +247,7 @@ class F16Step:
         if n > 0:
             deltas = _lib.AggDeltas(self.d[3].data_ptr(), self.d[2].data_ptr(), self.d[1].data_ptr(),
                                     self.d[0].data_ptr(), self.h4.data_ptr(), self.dza.data_ptr())
-            P = tr.points
-            grads = _lib.PointGrads(P.points_embeding.grad.data_ptr(), P.points_color.grad.data_ptr(),
-                                    P.points_dir.grad.data_ptr(), P.points_conf.grad.data_ptr())
+            grads = tr.point_grads()   # NULL members: frozen tensors
             _lib.check(L.sgn_aggregate_backward(*tr.variant, ctypes.byref(pt), ctypes.byref(qo), n, o.K,
                                                 _lib.ptr(blob), _lib.ptr(tblob), ctypes.byref(saved),
                                                 _lib.ptr(self.h2b), _lib.ptr(dfs), _lib.ptr(dal), _lib.ptr(scale),
@@ -304,8 +303,8 @@ class F16Step:
         Sc = min(cap, -(-max(S, 1) // GRAPH_BUCKET) * GRAPH_BUCKET)
         Nc = min(Sc, -(-max(n, 1) // GRAPH_BUCKET) * GRAPH_BUCKET)
         key = (R, Sc, Nc, q.work.data_ptr(), q.counters.data_ptr(), self.fs.data_ptr(), self.feat.data_ptr(),
-               fl.data_ptr(), fl.grad.data_ptr(), P.points_conf.data_ptr(), P.points_conf.grad.data_ptr(),
-               bg_ray is not None)
+               fl.data_ptr(), fl.grad.data_ptr(), P.points_conf.data_ptr(),
+               None if P.points_conf.grad is None else P.points_conf.grad.data_ptr(), bg_ray is not None)
         st = self._graphs.pop(key, None)
         if st is not None:
             self._graphs[key] = st              # most recently used goes last (LRU eviction order)
@@ -329,7 +328,8 @@ class F16Step:
                                           zero_dfs=True)
             st["segs"] = (_lib.PartialSegment * len(col.segments))(*col.segments)
             st["bpack"] = _attach_bpack(col.gemms, dev)
-            keep = [fl.grad.clone(), P.points_conf.grad.clone()]   # warm-up accumulates into them
+            cg = P.points_conf.grad   # None: conf is frozen, the stage writes no d conf
+            keep = [fl.grad.clone(), None if cg is None else cg.clone()]   # warm-up accumulates into them
             side = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
@@ -350,7 +350,8 @@ class F16Step:
                 if gc_on:
                     gc.enable()
             fl.grad.copy_(keep[0])
-            P.points_conf.grad.copy_(keep[1])
+            if cg is not None:
+                cg.copy_(keep[1])
             st["graph"] = g
             self._graphs[key] = st
         # the step's inputs into the graph's static buffers: one launch

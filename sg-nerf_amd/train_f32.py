@@ -279,7 +279,8 @@ class F32Step:
         self.vpe = torch.empty(cap, 32, **f32)
         self.d = [torch.empty(rows, 256, **f32) for _ in range(3)]      # delta1, delta2, delta3
         self.dext = torch.empty(rows, 8, **f32)
-        self.dx0 = torch.empty(rows, 224, **f32)
+        # block1.0's input gradient feeds d points_embeding alone: frozen, neither the buffer nor its GEMM exists
+        self.dx0 = torch.empty(rows, 224, **f32) if "points_embeding" in trainer.trained else None
         self.amax = torch.zeros(16, dtype=torch.int32, device=dev)
         self.dfeat = torch.empty(cap, 4, **f32)
         # the colour MLP and the losses over the items (their count at counts[0]), all products split-fp16
@@ -326,8 +327,10 @@ class F32Step:
         G.append(("d1", _rows_gemm(_operand(d2, 256, 256, 0, amax=amax[self.A_D2]), _operand(w, i_, i_, 1, shift=S("block1.2")),
                                    rc, 256, 256, n_rows, d1, 256, mask=z1, ldm=256, amax_out=amax[self.A_D1])))
         w, o_, i_ = W("block1.0")
-        G.append(("dx0", _rows_gemm(_operand(d1, 256, 256, 0, amax=amax[self.A_D1]), _operand(w, i_, 224, 1, shift=S("block1.0")),
-                                    rc, 224, 256, n_rows, _addr(self.dx0), 224)))
+        if self.dx0 is not None:
+            G.append(("dx0", _rows_gemm(_operand(d1, 256, 256, 0, amax=amax[self.A_D1]),
+                                        _operand(w, i_, 224, 1, shift=S("block1.0")), rc, 224, 256, n_rows,
+                                        _addr(self.dx0), 224)))
         self.g_row_bwd = G
         # ---- row weight gradients: delta^T [x | 1] ---------------------------------------------
         pr = self.part_rows
@@ -398,8 +401,7 @@ class F32Step:
                                 ctypes.c_void_p(_addr(self.amax, self.A_D4)), p(self.part_a), st), "sgn_train_row_head")
         for _, gs in self.g_row_bwd:
             gemm(gs)
-        grads = _lib.PointGrads(P.points_embeding.grad.data_ptr(), P.points_color.grad.data_ptr(),
-                                P.points_dir.grad.data_ptr(), P.points_conf.grad.data_ptr())
+        grads = tr.point_grads()   # NULL members: frozen tensors (all of embedding / colour / dir: no launch)
         ck(L.sgn_train_row_tail(ctypes.byref(pt), ctypes.byref(qo), K, p(self.row_off), p(self.counts), p(self.dx0),
                                 p(self.dext), ctypes.byref(grads), st), "sgn_train_row_tail")
         for gs in self.g_row_dw:
@@ -430,30 +432,6 @@ class F32Runner:
         self._blob = None        # this step's fp32-faithful blob (begin)
         self._rows = None        # this step's touched points: (int32 list, device count)
         self._t_idx = self._t_cnt = None   # under DP: touched_rows' list and count
-        # without the row-sparse Adam the touched list comes from sgn_touched_points' stamp table
-        self._stamp = self._tlist = self._tcount = None
-        self._stamp_n, self._tstep = -1, 0
-
-    def _touched(self, q, npts):
-        """The step's touched points (sgn_touched_points: an int32 list in no particular order and
-        its device count), for the single-GPU projection subset; no host sync, one launch."""
-        tr, dev = self.tr, self.tr.device
-        if self._stamp_n != npts:
-            self._stamp = torch.full((npts,), -1, dtype=torch.int32, device=dev)
-            self._tlist = torch.empty(npts, dtype=torch.int32, device=dev)
-            self._tcount = torch.zeros(3, dtype=torch.int64, device=dev)   # [2]: out-of-range ids met
-            self._stamp_n, self._tstep = npts, 0
-        step = self._tstep
-        self._tstep = (step + 1) & 0x7fffffff
-        if self._tstep == 0:   # the stamp table outlived 2^31 steps: start it again
-            self._stamp_n = -1
-        K = tr.opts.K
-        tr._check_oob()
-        _lib.check(_lib.lib().sgn_touched_points(_lib.ptr(q.pidx), _lib.ptr(q.counters), q.pidx.numel() // K, K, npts,
-                                                 step, _lib.ptr(self._stamp), _lib.ptr(self._tlist),
-                                                 _lib.ptr(self._tcount), _lib.stream_handle()), "sgn_touched_points")
-        tr._watch_oob(self._tcount[2:3])
-        return self._tlist, self._tcount[step & 1]
 
     def begin(self, b):
         """What the step queues before the gradients are made ready: the blob and the point Adam's launch."""
@@ -463,9 +441,10 @@ class F32Runner:
         if b.dp:   # every rank's touched rows ride the step's one sync (the point-row exchange)
             self._t_idx, self._t_cnt = touched_rows(q.pidx, q.counters[0], K, npts)
             self._rows = (self._t_idx.to(torch.int32), self._t_cnt)
-            tr._adam_rows(*self._rows, True, 1)
+            if tr._adam_rows(*self._rows, True, 1) is None and not tr.point_params:
+                tr.touched_points(q)   # every point tensor frozen: the OOB watch still sees the step
         else:      # the Adam's distinct-row list is the step's touched list (row 0 included)
-            self._rows = tr._adam_rows(q.pidx, q.counters, False, K) or self._touched(q, npts)
+            self._rows = tr._adam_rows(q.pidx, q.counters, False, K) or tr.touched_points(q)
 
     def run(self, b):
         """Forward + backward of the batch into the (ready) gradients.  Returns (loss parts, rendered

@@ -26,6 +26,10 @@ fp32 accumulation, train_f16.F16Step: one host sync per step, the loss stage as 
 sgn_adam_step_multi, the points' on the row-sparse exact sgn_adam_rows (PointAdam(rows=True):
 bit-identical to the dense update, applied at the next step's launch or at a flush).  The plane
 background model's per-ray colour (inputs['bg_ray']) enters the loss stage as T_bg * bg_ray.
+
+Which point tensors train follows opts.feat_grad / color_grad / dir_grad / conf_grad (neural_points.py:410-416):
+a frozen tensor's gradient pointer is NULL at the C ABI (no kernel computes it), it is in no point-Adam group
+and the data-parallel row exchange does not carry it.
 """
 from types import SimpleNamespace
 
@@ -35,9 +39,12 @@ import torch.distributed as dist
 from . import _lib
 from .flat_mlp import FlatMLP, _Packer, _PackerF32  # noqa: F401  (re-exported)
 from .opts import HotPathOpts
-from .point_adam import PointAdam
+from .point_adam import NoPointAdam, PointAdam
 from .train import PointParams, _allreduce_buckets, _allreduce_point_rows
 from .weights import layers_for
+
+
+POINT_TENSORS = ("points_embeding", "points_color", "points_dir", "points_conf")
 
 
 class HipTrainer:
@@ -71,7 +78,16 @@ class HipTrainer:
                                                  _lib.stream_handle()), "sgn_bpnet_pack")
             if precision == "f32":   # the fp32 kernels read the embedding as it is
                 self.bpnet32 = e
-        self.point_params = [points.points_embeding, points.points_color, points.points_dir, points.points_conf]
+        # opt.feat_grad / color_grad / dir_grad / conf_grad (neural_points.py:410-416): a frozen tensor takes
+        # no gradient (its kernels' outputs are NULL), has no Adam moments and never changes;
+        # point_params are the trained ones, in the point group's order
+        every = {k: getattr(points, k) for k in POINT_TENSORS}
+        self.trained = self.opts.trained_points
+        for k, p in every.items():
+            p.requires_grad_(k in self.trained)
+            if k not in self.trained:
+                p.grad = None
+        self.point_params = [every[k] for k in self.trained]
         # the reference's two Adam groups (mvs_points_volumetric_model.py:100-108); fused: one
         # kernel per group (sgn_adam_step, which also clears the gradient for the next step) instead
         # of the foreach chain; the MLP group's flat 0.35 M elements the same way
@@ -81,10 +97,13 @@ class HipTrainer:
             # row-sparse exact mode: a step updates the ~50 k rows it touches (each first replaying the
             # zero-gradient steps it missed) instead of streaming all 47 M elements; flushed before
             # anything else reads the points (sync_points)
-            self.opt_pts = PointAdam(self.point_params, lr=plr, betas=(0.9, 0.999), rows=True)
-        else:
+            # (row 0 is brought forward with every step only while conf trains: empty slots read its conf)
+            self.opt_pts = (PointAdam(self.point_params, lr=plr, betas=(0.9, 0.999), rows=True, names=self.trained,
+                                      row0="points_conf" in self.trained)
+                            if self.point_params else NoPointAdam(plr))
+        else:   # the reference's way: every tensor listed, the frozen ones without a gradient
             self.opt_net = torch.optim.Adam([self.mlp.flat], lr=lr, betas=(0.9, 0.999))
-            self.opt_pts = torch.optim.Adam(self.point_params, lr=plr, betas=(0.9, 0.999))
+            self.opt_pts = torch.optim.Adam(list(every.values()), lr=plr, betas=(0.9, 0.999))
         self._grads_clean = False  # the optimizers left every gradient zeroed
         self.base_lr = (lr, plr)
         self.decay = (lr_decay_exp, lr_decay_iters)
@@ -100,6 +119,9 @@ class HipTrainer:
         self._oob_host = torch.zeros(1, dtype=torch.int64, pin_memory=cuda)
         self._oob_event = torch.cuda.Event() if cuda else None
         self._oob_pending = False
+        # without a row-sparse Adam launch the OOB count comes from sgn_touched_points' stamp table
+        self._stamp = self._tlist = self._tcount = None
+        self._stamp_n, self._tstep = -1, 0
         # f16: the loss stage replays as a captured HIP graph; False runs the same stage eagerly (torch
         # autograd of the colour MLP into the HIP loss stage), the graph's parity reference in the tests
         self.use_graph = True
@@ -163,6 +185,33 @@ class HipTrainer:
     def check_touched(self):
         """Wait for and check the last step's out-of-range neighbour counter (see _check_oob)."""
         self._check_oob(wait=True)
+
+    def touched_points(self, q):
+        """The step's touched points (sgn_touched_points: an int32 list in no particular order and its
+        device count) where no row-sparse Adam launch lists them -- the dense Adam, or every point tensor
+        frozen; no host sync, one launch.  Its out-of-range count goes to the OOB watch."""
+        dev, npts = self.device, self.points.xyz.shape[0]
+        if self._stamp_n != npts:
+            self._stamp = torch.full((npts,), -1, dtype=torch.int32, device=dev)
+            self._tlist = torch.empty(npts, dtype=torch.int32, device=dev)
+            self._tcount = torch.zeros(3, dtype=torch.int64, device=dev)   # [2]: out-of-range ids met
+            self._stamp_n, self._tstep = npts, 0
+        step = self._tstep
+        self._tstep = (step + 1) & 0x7fffffff
+        if self._tstep == 0:   # the stamp table outlived 2^31 steps: start it again
+            self._stamp_n = -1
+        K = self.opts.K
+        self._check_oob()
+        _lib.check(_lib.lib().sgn_touched_points(_lib.ptr(q.pidx), _lib.ptr(q.counters), q.pidx.numel() // K, K, npts,
+                                                 step, _lib.ptr(self._stamp), _lib.ptr(self._tlist),
+                                                 _lib.ptr(self._tcount), _lib.stream_handle()), "sgn_touched_points")
+        self._watch_oob(self._tcount[2:3])
+        return self._tlist, self._tcount[step & 1]
+
+    def point_grads(self):
+        """The point gradients as the kernels take them (sgn_point_grads): NULL for a frozen tensor."""
+        g = [getattr(self.points, k).grad for k in POINT_TENSORS]
+        return _lib.PointGrads(*[None if t is None else t.data_ptr() for t in g])
 
     # -- row-sparse point Adam --------------------------------------------------------------
     def _rows_adam(self):
@@ -241,7 +290,7 @@ class HipTrainer:
         self._grads_clean = False
         parts, full, ray_mask = step.run(b)
         self.allreduce_grads([self.mlp.flat])
-        if dp:
+        if dp and self.point_params:   # the sparse row exchange carries the trained tensors only
             self._adam_union(_allreduce_point_rows([p.grad for p in self.point_params], *step.dp_rows()))
         return parts, full, ray_mask.bool()
 
@@ -268,7 +317,8 @@ class HipTrainer:
         self._set_lr()
         self.opt_net.step()
         self.opt_pts.step()
-        self._grads_clean = all(isinstance(o, PointAdam) and o.zero_grad_in_step for o in (self.opt_net, self.opt_pts))
+        self._grads_clean = all(isinstance(o, (PointAdam, NoPointAdam)) and o.zero_grad_in_step
+                                for o in (self.opt_net, self.opt_pts))
         self.step_count += 1
 
     def step(self, campos, rot, raydir, near, far, gt, labels=None, bg_ray=None):
@@ -289,6 +339,7 @@ def grads_named(trainer: HipTrainer):
         out[name + ".weight"] = m.w(name, g).detach().clone()
         out[name + ".bias"] = m.b(name, g).detach().clone()
     P = trainer.points
-    for k in ("points_embeding", "points_color", "points_dir", "points_conf"):
-        out[k] = getattr(P, k).grad.detach().clone()
+    for k in POINT_TENSORS:   # a frozen tensor has none
+        g = getattr(P, k).grad
+        out[k] = None if g is None else g.detach().clone()
     return out
