@@ -683,6 +683,17 @@ int sgn_composite(const sgn_composite_params *cp, const float *d_campos, const f
                   int8_t *d_out_mask, float *d_out_bgT, float *d_out_opacity, float *d_out_blendw,
                   sgn_stream_t stream);
 
+/* sgn_composite plus a depth map: d_out_depth float[R] (required) = D_r = A_r / (W_r + 1e-6) with
+ * W_r = sum_s w_s and A_r = sum_s w_s z_s in fp32 over the slots in ascending order, w_s the alpha-blend
+ * weight (out_blendw's value) and z_s the camera-space z of slot s's sample (the value ray_dist's cummax
+ * reads, taken raw; reference coarse_depth, neural_points_volumetric_model.py:620-624).  A ray without a
+ * valid sample (out_mask 0) gets 0.  Every other output is sgn_composite's, bit for bit. */
+int sgn_composite_depth(const sgn_composite_params *cp, const float *d_campos, const float *d_camrotc2w,
+                        const float *d_raydir, int64_t R, const float *d_t_table, int32_t per_ray_t,
+                        int32_t D, const sgn_query_out *q, const float *d_feat, float *d_out_rgb,
+                        int8_t *d_out_mask, float *d_out_bgT, float *d_out_opacity, float *d_out_blendw,
+                        float *d_out_depth, sgn_stream_t stream);
+
 /* ray_march on dense [R, SR] inputs (diff_ray_marching.py:509-555, alpha blend +
  * radiance render): ray_dist/valid/feat(float4) in, rgb[R*3] (+ bg*T if bg != NULL,
  * host pointer to 3 floats), opacity/acc_transmission/blend_weight[R*SR], bg T[R]. */
@@ -748,6 +759,28 @@ int sgn_loss_train(const sgn_loss_params *lp, const float *d_campos, const float
                    const sgn_query_out *q, const float *d_feat, const float *d_gt, const float *d_conf,
                    float *d_out_rgb, int8_t *d_out_mask, float *d_losses, float *d_dfeat, float *d_dconf,
                    void *d_workspace, size_t workspace_bytes, sgn_stream_t stream);
+
+/* The loss stage with depth supervision (depth_loss_items = coarse_depth, base_rendering_model.py:611-618):
+ * sgn_loss_train plus, per ray, D_r as sgn_composite_depth defines it into out_depth float[R] (0 for a ray
+ * with out_mask 0), d_losses[7] = L_depth = (1/R) sum over all R rays of (m_r (D_r - gt_depth_r))^2 with
+ * m_r = gt_mask_r, or gt_depth_r > 0 when gt_mask is NULL, and d_dfeat[.].x (sigma) carrying in addition
+ * weight * d L_depth / d sigma (through w_s only: d D_r / d w_s = (z_s - D_r) / (W_r + 1e-6); rays with
+ * out_mask 0 get no gradient).  total = sgn_loss_train's + weight * d_losses[7].  weight == 0 leaves every
+ * output of sgn_loss_train bit for bit.  gt_depth and out_depth are required; the workspace is sized by
+ * sgn_loss_depth_workspace_bytes.  Three launches, no host synchronisation. */
+typedef struct {
+    const float *gt_depth;     /* device float[R] */
+    const float *gt_mask;      /* device float[R]; NULL: gt_depth > 0 */
+    float weight;              /* depth_loss_weights[i] */
+    float *out_depth;          /* device float[R] */
+} sgn_loss_depth;
+
+size_t sgn_loss_depth_workspace_bytes(int64_t R, int32_t SR);
+int sgn_loss_train_depth(const sgn_loss_params *lp, const sgn_loss_depth *dp, const float *d_campos,
+                         const float *d_camrotc2w, int64_t R, const sgn_query_out *q, const float *d_feat,
+                         const float *d_gt, const float *d_conf, float *d_out_rgb, int8_t *d_out_mask,
+                         float *d_losses, float *d_dfeat, float *d_dconf, void *d_workspace, size_t workspace_bytes,
+                         sgn_stream_t stream);
 
 /* ---- misc -------------------------------------------------------------- */
 int sgn_abi_version(void);

@@ -70,6 +70,10 @@ class LossParams(ctypes.Structure):
                 ("zero_one_weight", c_f32), ("zero_one_eps", c_f32), ("bg_ray", c_vp)]
 
 
+class LossDepth(ctypes.Structure):
+    _fields_ = [("gt_depth", c_vp), ("gt_mask", c_vp), ("weight", c_f32), ("out_depth", c_vp)]
+
+
 class GradSegment(ctypes.Structure):
     _fields_ = [("src", c_vp), ("tail", c_vp), ("dst", c_vp), ("n", c_i64), ("stride", c_i64), ("nb", c_i32),
                 ("reserved", c_i32)]
@@ -199,11 +203,17 @@ SIGNATURES = {
     "sgn_mlp_pack_index_f32": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_i64]),
     "sgn_composite": (c_i32, [ctypes.POINTER(CompositeParams), c_vp, c_vp, c_vp, c_i64, c_vp, c_i32,
                               c_i32, ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgn_composite_depth": (c_i32, [ctypes.POINTER(CompositeParams), c_vp, c_vp, c_vp, c_i64, c_vp, c_i32,
+                                    c_i32, ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgn_probe": (c_i32, [ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_i64, c_i32, c_i32,
                           c_vp, c_vp]),
     "sgn_loss_workspace_bytes": (c_sz, [c_i64, c_i32]),
     "sgn_loss_train": (c_i32, [ctypes.POINTER(LossParams), c_vp, c_vp, c_i64, ctypes.POINTER(QueryOut), c_vp, c_vp,
                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "sgn_loss_depth_workspace_bytes": (c_sz, [c_i64, c_i32]),
+    "sgn_loss_train_depth": (c_i32, [ctypes.POINTER(LossParams), ctypes.POINTER(LossDepth), c_vp, c_vp, c_i64,
+                                     ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_sz, c_vp]),
     "sgn_ray_march_dense": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, ctypes.POINTER(c_f32), c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_vp]),
 }

@@ -10,6 +10,8 @@
 //   fill_invalid    neural_points_volumetric_model.py:158-195 (rays without a valid
 //                   sample get bg, coarse_is_background 1, ray_mask 0)
 // One thread per ray, single pass over the slots (running cummax, running T).
+#include <type_traits>
+
 #include "sgn_common.h"
 
 namespace sgn {
@@ -24,6 +26,10 @@ struct CompArgs {
     float vz, bg0, bg1, bg2;
     float *out_rgb, *out_bgT, *out_opacity, *out_blendw;
     int8_t *out_mask;
+};
+// sgn_composite_depth's arguments: the stock block first (k_composite<false> is passed a plain CompArgs)
+struct CompDepthArgs : CompArgs {
+    float *out_depth;
 };
 
 __device__ __forceinline__ float pers_z(const float *campos, const float *rot, float x, float y, float z) {
@@ -60,7 +66,11 @@ __device__ __forceinline__ void store_chunk(float *dst, const float *st, int SR,
     }
 }
 
-__global__ __launch_bounds__(COMP_RAYS) void k_composite(CompArgs a) {
+// DEPTH (sgn_composite_depth): two more running sums per ray, W = sum w_s and A = sum w_s z_s (z_s the raw
+// pers z of slot s's sample, the value the cummax reads), and out_depth = A / (W + 1e-6), 0 for a ray
+// without a valid sample.  The DEPTH = false instantiation is the stock kernel.
+template <bool DEPTH>
+__global__ __launch_bounds__(COMP_RAYS) void k_composite(std::conditional_t<DEPTH, CompDepthArgs, CompArgs> a) {
     __shared__ float st[2][COMP_RAYS * COMP_LD];  // chunk staging: opacity, blend weight
     const int lane = threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * COMP_RAYS, r = r0 + lane;
@@ -77,6 +87,7 @@ __global__ __launch_bounds__(COMP_RAYS) void k_composite(CompArgs a) {
     // slot s-1 state while slot s's z is read
     bool pv = false;
     float4 pf = make_float4(0.f, 0.f, 0.f, 0.f);
+    float pz = 0.f, dW = 0.f, dA = 0.f;  // DEPTH: slot s-1's z, the running sums
     int c0 = 0;  // the chunk being staged: slot s lands at column s - c0
     auto process = [&](int slot, float dist) {
         const bool mask = dist < 1e-8f || (a.unit && dist > 2.f * a.vz);
@@ -90,6 +101,10 @@ __global__ __launch_bounds__(COMP_RAYS) void k_composite(CompArgs a) {
             cr += pf.y * wgt;
             cg += pf.z * wgt;
             cb += pf.w * wgt;
+            if constexpr (DEPTH) {
+                dW += wgt;
+                dA += wgt * pz;
+            }
         }
         if (want_b) sb[slot - c0] = wgt;
         T = T * (1.f - o + 1e-10f);
@@ -112,6 +127,7 @@ __global__ __launch_bounds__(COMP_RAYS) void k_composite(CompArgs a) {
         prev_cm = cm;
         pv = v;
         pf = f;
+        if constexpr (DEPTH) pz = z;
         any_valid |= v;
     };
     if (last >= 0) step(0);
@@ -139,6 +155,7 @@ __global__ __launch_bounds__(COMP_RAYS) void k_composite(CompArgs a) {
         a.out_rgb[r * 3 + 1] = any_valid ? cg + a.bg1 * T : a.bg1;
         a.out_rgb[r * 3 + 2] = any_valid ? cb + a.bg2 * T : a.bg2;
         if (a.out_bgT) a.out_bgT[r] = any_valid ? T : 1.f;
+        if constexpr (DEPTH) a.out_depth[r] = any_valid ? dA / (dW + 1e-6f) : 0.f;
     }
 }
 
@@ -199,17 +216,18 @@ extern "C" int sgn_ray_march_dense(const float *d_ray_dist, const uint8_t *d_val
     return 0;
 }
 
-extern "C" int sgn_composite(const sgn_composite_params *cp, const float *d_campos, const float *d_camrotc2w,
-                             const float *d_raydir, int64_t R, const float *d_t_table, int32_t per_ray_t,
-                             int32_t D, const sgn_query_out *q, const float *d_feat, float *d_out_rgb,
-                             int8_t *d_out_mask, float *d_out_bgT, float *d_out_opacity, float *d_out_blendw,
-                             sgn_stream_t stream) {
-    using namespace sgn;
-    (void)d_t_table; (void)per_ray_t; (void)D;
-    SGN_REQUIRE(cp && q && d_feat && d_out_rgb && d_out_mask, "null argument");
+namespace sgn {
+namespace {
+
+template <bool DEPTH>
+int composite_launch(const sgn_composite_params *cp, const float *d_campos, const float *d_camrotc2w,
+                     const float *d_raydir, int64_t R, const sgn_query_out *q, const float *d_feat, float *d_out_rgb,
+                     int8_t *d_out_mask, float *d_out_bgT, float *d_out_opacity, float *d_out_blendw,
+                     float *d_out_depth, sgn_stream_t stream) {
+    SGN_REQUIRE(cp && q && d_feat && d_out_rgb && d_out_mask && (!DEPTH || d_out_depth), "null argument");
     SGN_REQUIRE(cp->SR > 0, "SR must be positive");
     if (R == 0) return 0;
-    CompArgs a;
+    std::conditional_t<DEPTH, CompDepthArgs, CompArgs> a;
     a.campos = d_campos; a.rot = d_camrotc2w; a.raydir = d_raydir;
     a.ray_ns = q->ray_ns; a.ray_soff = q->ray_soff; a.samp_nnb = q->samp_nnb;
     a.samp_locw = q->samp_locw; a.feat = d_feat;
@@ -217,8 +235,32 @@ extern "C" int sgn_composite(const sgn_composite_params *cp, const float *d_camp
     a.bg0 = cp->bg[0]; a.bg1 = cp->bg[1]; a.bg2 = cp->bg[2];
     a.out_rgb = d_out_rgb; a.out_bgT = d_out_bgT; a.out_opacity = d_out_opacity; a.out_mask = d_out_mask;
     a.out_blendw = d_out_blendw;
-    hipLaunchKernelGGL(k_composite, dim3((unsigned)((R + COMP_RAYS - 1) / COMP_RAYS)), dim3(COMP_RAYS), 0,
+    if constexpr (DEPTH) a.out_depth = d_out_depth;
+    hipLaunchKernelGGL(k_composite<DEPTH>, dim3((unsigned)((R + COMP_RAYS - 1) / COMP_RAYS)), dim3(COMP_RAYS), 0,
                        as_stream(stream), a);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+}  // namespace
+}  // namespace sgn
+
+extern "C" int sgn_composite(const sgn_composite_params *cp, const float *d_campos, const float *d_camrotc2w,
+                             const float *d_raydir, int64_t R, const float *d_t_table, int32_t per_ray_t,
+                             int32_t D, const sgn_query_out *q, const float *d_feat, float *d_out_rgb,
+                             int8_t *d_out_mask, float *d_out_bgT, float *d_out_opacity, float *d_out_blendw,
+                             sgn_stream_t stream) {
+    (void)d_t_table; (void)per_ray_t; (void)D;
+    return sgn::composite_launch<false>(cp, d_campos, d_camrotc2w, d_raydir, R, q, d_feat, d_out_rgb, d_out_mask,
+                                        d_out_bgT, d_out_opacity, d_out_blendw, nullptr, stream);
+}
+
+extern "C" int sgn_composite_depth(const sgn_composite_params *cp, const float *d_campos, const float *d_camrotc2w,
+                                   const float *d_raydir, int64_t R, const float *d_t_table, int32_t per_ray_t,
+                                   int32_t D, const sgn_query_out *q, const float *d_feat, float *d_out_rgb,
+                                   int8_t *d_out_mask, float *d_out_bgT, float *d_out_opacity, float *d_out_blendw,
+                                   float *d_out_depth, sgn_stream_t stream) {
+    (void)d_t_table; (void)per_ray_t; (void)D;
+    return sgn::composite_launch<true>(cp, d_campos, d_camrotc2w, d_raydir, R, q, d_feat, d_out_rgb, d_out_mask,
+                                       d_out_bgT, d_out_opacity, d_out_blendw, d_out_depth, stream);
 }

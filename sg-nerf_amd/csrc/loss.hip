@@ -17,6 +17,15 @@
 //                  gradient scales (the valid-ray count is only known here)
 //   k_loss_bwd     8 lanes per ray: reverse pass over the slots -> d feat per sample;
 //                  zero-one gradients added into d conf (atomics; a ray's empty entries as one add)
+// Depth supervision (sgn_loss_train_depth) runs the DEPTH = true instantiations of the same three kernels:
+// per ray W = sum w_s, A = sum w_s z_s (w_s = o_s T_s, z_s the raw pers z the cummax reads),
+// D = A / (W + 1e-6) (neural_points_volumetric_model.py:620-624), 0 for a ray without a valid sample;
+// L_depth = mean over all R rays of (m (D - gt_depth))^2 (base_rendering_model.py:611-618) goes to the
+// loss vector's slot 7, and the reverse pass carries one more "colour channel" with the per-slot value
+// q_s = (z_s - D) / (W + 1e-6) and the weight d total / d D (no background term).  The DEPTH = false
+// instantiations are the stock kernels (they are passed a plain LossArgs).
+#include <type_traits>
+
 #include "sgn_common.h"
 
 namespace sgn {
@@ -43,6 +52,23 @@ struct LossArgs {
     float *dfeat;     // [S][4]
     float *dconf;     // [N]
 };
+
+// sgn_loss_train_depth's arguments: the stock block first
+struct LossDepthArgs : LossArgs {
+    const float *gt_depth;  // [R]
+    const float *gt_mask;   // [R] float mask or null: gt_depth > 0
+    float depth_w;          // depth_loss_weights[i]: scales the depth term's gradient only
+    float *out_depth;       // [R] D
+    float *ray_w;           // [R] W (workspace), read by the reverse pass
+};
+template <bool DEPTH>
+using loss_args_t = std::conditional_t<DEPTH, LossDepthArgs, LossArgs>;
+template <bool DEPTH>
+constexpr int loss_nsum = DEPTH ? LOSS_NSUM + 1 : LOSS_NSUM;  // + the depth term's squared error
+
+__device__ __forceinline__ float depth_mask(const LossDepthArgs &a, int64_t r, float g) {
+    return a.gt_mask ? a.gt_mask[r] : (g > 0.f ? 1.f : 0.f);
+}
 
 // the ray's background colour: inputs['bg_ray'] when given (fill_invalid blends T_bg * bg_ray,
 // neural_points_volumetric_model.py:175-177), else the constant bg
@@ -71,8 +97,10 @@ __device__ __forceinline__ void zero_one(float cd, float eps, float &term, float
 
 // Per ray forward: slot s of the ray (s < ns: sample soff + s; later slots are padding at the
 // origin's depth) closes slot s - 1's interval (running cummax of pers z).
-template <bool STORE>
-__device__ void ray_forward(const LossArgs &a, int64_t r, bool store, float (&col)[3], float &T, bool &any_valid) {
+// DEPTH: also dW = sum w_s and dA = sum w_s z_s over the slots in ascending order.
+template <bool STORE, bool DEPTH>
+__device__ void ray_forward(const LossArgs &a, int64_t r, bool store, float (&col)[3], float &T, bool &any_valid,
+                            float &dW, float &dA) {
     const int ns = a.ray_ns[r], off = a.ray_soff[r], SR = a.SR;
     const float z0 = pers_z(a.campos, a.rot, 0.f, 0.f, 0.f);
     float *ws = a.slot_ws + r * (int64_t)SR * 3;
@@ -82,6 +110,8 @@ __device__ void ray_forward(const LossArgs &a, int64_t r, bool store, float (&co
     float prev_cm = 0.f;
     bool pv = false;
     float4 pf = make_float4(0.f, 0.f, 0.f, 0.f);
+    float pz = 0.f;  // DEPTH: slot s - 1's z
+    if constexpr (DEPTH) dW = dA = 0.f;
     auto process = [&](int slot, float dist) {
         const bool mask = dist < 1e-8f || (a.unit && dist > 2.f * a.vz);
         dist = mask ? a.vz : dist;
@@ -94,6 +124,10 @@ __device__ void ray_forward(const LossArgs &a, int64_t r, bool store, float (&co
         col[0] += pf.y * wgt;
         col[1] += pf.z * wgt;
         col[2] += pf.w * wgt;
+        if constexpr (DEPTH) {
+            dW += wgt;
+            dA += wgt * pz;
+        }
         if (STORE && store) {
             ws[3 * slot + 0] = T;
             ws[3 * slot + 1] = e;
@@ -117,6 +151,7 @@ __device__ void ray_forward(const LossArgs &a, int64_t r, bool store, float (&co
         prev_cm = cm;
         pv = v;
         pf = f;
+        if constexpr (DEPTH) pz = z;
         any_valid |= v;
     }
     if (ns >= SR) process(SR - 1, a.vz);
@@ -133,15 +168,17 @@ __device__ __forceinline__ float block_sum(float v, float *red) {
     return t;
 }
 
-__global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(LossArgs a) {
+template <bool DEPTH>
+__global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(loss_args_t<DEPTH> a) {
+    constexpr int NSUM = loss_nsum<DEPTH>;
     __shared__ float red[LOSS_TPB / 64];
     const int64_t r = ((int64_t)blockIdx.x * LOSS_TPB + threadIdx.x) / LPR;
     const int sub = threadIdx.x % LPR;
-    float v[LOSS_NSUM] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float v[NSUM] = {};
     if (r < a.R) {
-        float col[3], T;
+        float col[3], T, dW, dA;
         bool any;
-        ray_forward<true>(a, r, sub == 0, col, T, any);
+        ray_forward<true, DEPTH>(a, r, sub == 0, col, T, any, dW, dA);
         float bg[3];
         ray_bg(a, r, bg);
         float se = 0.f;
@@ -157,6 +194,14 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(LossArgs a) {
             v[1] = any ? 0.f : se;
             v[2] = se;
             v[4] = any ? 1.f : 0.f;
+            if constexpr (DEPTH) {  // every ray counts: a ray without a valid sample has D = 0
+                const float D = any ? dA / (dW + 1e-6f) : 0.f;
+                a.out_depth[r] = D;
+                a.ray_w[r] = dW;
+                const float g = a.gt_depth[r];
+                const float md = depth_mask(a, r, g) * (D - g);
+                v[NSUM - 1] = md * md;
+            }
         }
         if (any) {  // zero-one terms over the ray's SR x K entries, neighbour k = sub, sub + 8, ..
             const int ns = a.ray_ns[r], off = a.ray_soff[r];
@@ -181,18 +226,20 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(LossArgs a) {
             v[3] = zs + (float)n_empty * t0;
         }
     }
-    for (int i = 0; i < LOSS_NSUM; ++i) {
+    for (int i = 0; i < NSUM; ++i) {
         const float t = block_sum(v[i], red);
-        if (threadIdx.x == 0) a.partial[(int64_t)blockIdx.x * LOSS_NSUM + i] = t;
+        if (threadIdx.x == 0) a.partial[(int64_t)blockIdx.x * NSUM + i] = t;
     }
 }
 
-__global__ __launch_bounds__(LOSS_TPB) void k_loss_reduce(LossArgs a, int nblocks) {
+template <bool DEPTH>
+__global__ __launch_bounds__(LOSS_TPB) void k_loss_reduce(loss_args_t<DEPTH> a, int nblocks) {
+    constexpr int NSUM = loss_nsum<DEPTH>;
     __shared__ float red[LOSS_TPB / 64];
-    float t[LOSS_NSUM];
-    for (int i = 0; i < LOSS_NSUM; ++i) {
+    float t[NSUM];
+    for (int i = 0; i < NSUM; ++i) {
         float v = 0.f;
-        for (int b = threadIdx.x; b < nblocks; b += LOSS_TPB) v += a.partial[(int64_t)b * LOSS_NSUM + i];
+        for (int b = threadIdx.x; b < nblocks; b += LOSS_TPB) v += a.partial[(int64_t)b * NSUM + i];
         t[i] = block_sum(v, red);
     }
     if (threadIdx.x == 0) {
@@ -205,14 +252,17 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_reduce(LossArgs a, int nblock
         a.sums[4] = 2.f / den_c;
         a.sums[5] = a.zo_w / den_z;
         a.sums[6] = n;
-        a.sums[7] = 0.f;
+        if constexpr (DEPTH)
+            a.sums[7] = t[NSUM - 1] / (float)a.R;  // L_depth: MSELoss over all R rays
+        else
+            a.sums[7] = 0.f;
     }
 }
 
 // CONF: points_conf is trained (dconf non-NULL); frozen, the zero-one term is still in the loss
 // (k_loss_fwd) and only its gradient -- the loop below, point 0's empty-slot term included -- goes
-template <bool CONF>
-__global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(LossArgs a) {
+template <bool CONF, bool DEPTH>
+__global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(loss_args_t<DEPTH> a) {
     const int64_t r = ((int64_t)blockIdx.x * LOSS_TPB + threadIdx.x) / LPR;
     const int sub = threadIdx.x % LPR;
     if (r >= a.R) return;
@@ -238,12 +288,27 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(LossArgs a) {
         float bg[3];
         ray_bg(a, r, bg);
         float U = (g[0] * bg[0] + g[1] * bg[1] + g[2] * bg[2]) * Tend;
+        // DEPTH: gD = d total / d D of the ray, q_s = (z_s - D) / Wd; a zero gD leaves every bit as stock
+        float gD = 0.f, Dr = 0.f, Wd = 1.f;
+        if constexpr (DEPTH) {
+            const float gt_d = a.gt_depth[r], m = depth_mask(a, r, gt_d);
+            Dr = a.out_depth[r];
+            Wd = a.ray_w[r] + 1e-6f;
+            gD = a.depth_w * 2.f * (m * m) * (Dr - gt_d) / (float)a.R;
+        }
         for (int s = nv - 1; s >= 0; --s) {
             const int64_t id = off + s;
             const float T = ws[3 * s], e = ws[3 * s + 1], dist = ws[3 * s + 2];
             const float4 f = *(const float4 *)(a.feat + id * 4);
             const float o = 1.f - e;
-            const float gc = g[0] * f.y + g[1] * f.z + g[2] * f.w;
+            float gc = g[0] * f.y + g[1] * f.z + g[2] * f.w;
+            if constexpr (DEPTH) {
+                if (gD != 0.f) {
+                    const float z = pers_z(a.campos, a.rot, a.samp_locw[id * 3], a.samp_locw[id * 3 + 1],
+                                           a.samp_locw[id * 3 + 2]);
+                    gc += gD * ((z - Dr) / Wd);
+                }
+            }
             const float av = 1.f - o + 1e-10f;
             const float dO = gc * T - U / av;               // d L / d o_s
             const bool v = a.samp_nnb[id] > 0;
@@ -286,22 +351,25 @@ size_t sgn_loss_workspace_bytes(int64_t R, int32_t SR) {
     return (size_t)(R * SR * 3 * 4 + (nb + 1) * sgn::LOSS_NSUM * 4 + 64);
 }
 
-int sgn_loss_train(const sgn_loss_params *lp, const float *d_campos, const float *d_camrotc2w, int64_t R,
-                   const sgn_query_out *q, const float *d_feat, const float *d_gt, const float *d_conf,
-                   float *d_out_rgb, int8_t *d_out_mask, float *d_losses, float *d_dfeat, float *d_dconf,
-                   void *d_workspace, size_t workspace_bytes, sgn_stream_t stream) {
+static int loss_launch(const sgn_loss_params *lp, const sgn_loss_depth *dp, const float *d_campos,
+                       const float *d_camrotc2w, int64_t R, const sgn_query_out *q, const float *d_feat,
+                       const float *d_gt, const float *d_conf, float *d_out_rgb, int8_t *d_out_mask, float *d_losses,
+                       float *d_dfeat, float *d_dconf, void *d_workspace, size_t workspace_bytes, bool depth,
+                       sgn_stream_t stream) {
     using namespace sgn;
     SGN_REQUIRE(lp && q && d_campos && d_camrotc2w && d_feat && d_gt && d_conf && d_out_rgb && d_out_mask &&
                     d_losses && d_dfeat && d_workspace,
                 "null argument");
+    SGN_REQUIRE(!depth || (dp && dp->gt_depth && dp->out_depth), "null argument");
     SGN_REQUIRE(lp->SR > 0 && lp->K > 0, "SR and K must be positive");
     SGN_REQUIRE(R >= 0, "R must be non-negative");
-    SGN_REQUIRE(workspace_bytes >= sgn_loss_workspace_bytes(R, lp->SR), "loss workspace too small");
+    SGN_REQUIRE(workspace_bytes >= (depth ? sgn_loss_depth_workspace_bytes(R, lp->SR) : sgn_loss_workspace_bytes(R, lp->SR)),
+                "loss workspace too small");
     SGN_REQUIRE(((uintptr_t)d_feat & 15) == 0 && ((uintptr_t)d_dfeat & 15) == 0 && ((uintptr_t)d_workspace & 15) == 0,
                 "16-byte alignment required");
     hipStream_t st = as_stream(stream);
     const int64_t nb = (R * LPR + LOSS_TPB - 1) / LOSS_TPB;
-    LossArgs a{};
+    LossDepthArgs a{};
     a.campos = d_campos; a.rot = d_camrotc2w;
     a.ray_ns = q->ray_ns; a.ray_soff = q->ray_soff; a.samp_nnb = q->samp_nnb; a.pidx = q->pidx;
     a.samp_locw = q->samp_locw; a.feat = d_feat; a.gt = d_gt; a.conf = d_conf;
@@ -313,15 +381,51 @@ int sgn_loss_train(const sgn_loss_params *lp, const float *d_campos, const float
     a.partial = a.slot_ws + R * lp->SR * 3;
     a.sums = d_losses;
     a.out_rgb = d_out_rgb; a.out_mask = d_out_mask; a.dfeat = d_dfeat; a.dconf = d_dconf;
+    if (depth) {  // workspace: slots, W per ray, partials
+        a.gt_depth = dp->gt_depth; a.gt_mask = dp->gt_mask; a.depth_w = dp->weight; a.out_depth = dp->out_depth;
+        a.ray_w = a.partial;
+        a.partial = a.ray_w + R;
+    }
     if (R == 0) {
         SGN_CHECK_HIP(hipMemsetAsync(d_losses, 0, 8 * sizeof(float), st));
         return 0;
     }
-    hipLaunchKernelGGL(k_loss_fwd, dim3((unsigned)nb), dim3(LOSS_TPB), 0, st, a);
-    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(LOSS_TPB), 0, st, a, (int)nb);
-    hipLaunchKernelGGL(d_dconf ? k_loss_bwd<true> : k_loss_bwd<false>, dim3((unsigned)nb), dim3(LOSS_TPB), 0, st, a);
+    const dim3 grid((unsigned)nb), one(1), tpb(LOSS_TPB);
+    if (depth) {
+        hipLaunchKernelGGL(k_loss_fwd<true>, grid, tpb, 0, st, a);
+        hipLaunchKernelGGL(k_loss_reduce<true>, one, tpb, 0, st, a, (int)nb);
+        hipLaunchKernelGGL((d_dconf ? k_loss_bwd<true, true> : k_loss_bwd<false, true>), grid, tpb, 0, st, a);
+    } else {
+        const LossArgs &b = a;
+        hipLaunchKernelGGL(k_loss_fwd<false>, grid, tpb, 0, st, b);
+        hipLaunchKernelGGL(k_loss_reduce<false>, one, tpb, 0, st, b, (int)nb);
+        hipLaunchKernelGGL((d_dconf ? k_loss_bwd<true, false> : k_loss_bwd<false, false>), grid, tpb, 0, st, b);
+    }
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+size_t sgn_loss_depth_workspace_bytes(int64_t R, int32_t SR) {
+    if (R < 0 || SR <= 0) return 0;
+    const int64_t nb = (R * sgn::LPR + sgn::LOSS_TPB - 1) / sgn::LOSS_TPB;
+    return (size_t)(R * SR * 3 * 4 + R * 4 + (nb + 1) * (sgn::LOSS_NSUM + 1) * 4 + 64);
+}
+
+int sgn_loss_train(const sgn_loss_params *lp, const float *d_campos, const float *d_camrotc2w, int64_t R,
+                   const sgn_query_out *q, const float *d_feat, const float *d_gt, const float *d_conf,
+                   float *d_out_rgb, int8_t *d_out_mask, float *d_losses, float *d_dfeat, float *d_dconf,
+                   void *d_workspace, size_t workspace_bytes, sgn_stream_t stream) {
+    return loss_launch(lp, nullptr, d_campos, d_camrotc2w, R, q, d_feat, d_gt, d_conf, d_out_rgb, d_out_mask, d_losses,
+                       d_dfeat, d_dconf, d_workspace, workspace_bytes, false, stream);
+}
+
+int sgn_loss_train_depth(const sgn_loss_params *lp, const sgn_loss_depth *dp, const float *d_campos,
+                         const float *d_camrotc2w, int64_t R, const sgn_query_out *q, const float *d_feat,
+                         const float *d_gt, const float *d_conf, float *d_out_rgb, int8_t *d_out_mask,
+                         float *d_losses, float *d_dfeat, float *d_dconf, void *d_workspace, size_t workspace_bytes,
+                         sgn_stream_t stream) {
+    return loss_launch(lp, dp, d_campos, d_camrotc2w, R, q, d_feat, d_gt, d_conf, d_out_rgb, d_out_mask, d_losses,
+                       d_dfeat, d_dconf, d_workspace, workspace_bytes, true, stream);
 }
 
 }  // extern "C"

@@ -41,27 +41,32 @@ class LossStage:
         self.device = torch.device(device)
         self._key = None
 
-    def _buffers(self, R, SR):
+    def _buffers(self, R, SR, depth=False):
         """The workspace grows, never moves to a smaller one (a captured graph keeps the pointer it
         was captured with: HipTrainer gives every captured loss stage its own LossStage)."""
-        need = max(int(_lib.lib().sgn_loss_workspace_bytes(R, SR)), 16)
+        L = _lib.lib()
+        need = max(int(L.sgn_loss_depth_workspace_bytes(R, SR) if depth else L.sgn_loss_workspace_bytes(R, SR)), 16)
         if self._key is None or self.ws.numel() < need:
             self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._key = (R, SR)
         return self.ws
 
     def __call__(self, points, q_abi, feat, campos, rot, gt, opts: HotPathOpts, R, bg=(1.0, 1.0, 1.0),
-                 zero_one_weight=1e-4, zero_eps=1e-3, bg_ray=None):
+                 zero_one_weight=1e-4, zero_eps=1e-3, bg_ray=None, depth=None):
         """feat [S_cap, 4] fp32 per sample (alpha, r, g, b; zeros for samples without neighbours),
         q_abi: the query's sgn_query_out; bg_ray: the rays' background [R, 3] (device, replaces bg).
-        Returns (total, parts, full [R, 3], ray_mask [R] bool) as train.composite_losses."""
+        depth: a train.DepthTarget -- depth supervision on sgn_loss_train_depth, whose d feat carries the
+        depth term's gradient already scaled by depth.weight (backward scales it with losses[0]'s incoming
+        gradient, as the colour term's).
+        Returns (total, parts, full [R, 3], ray_mask [R] bool) and, with depth, the depth map [R], as
+        train.composite_losses."""
         dev = self.device
         conf = points.points_conf
         n_points = conf.shape[0]
         feat = feat.contiguous()
         if feat.shape[0] == 0:   # a batch without samples: one zero row keeps the pointers valid
             feat = torch.cat([feat, feat.new_zeros(1, 4)])
-        ws = self._buffers(R, opts.SR)
+        ws = self._buffers(R, opts.SR, depth is not None)
         campos = campos.reshape(3).to(dev, torch.float32).contiguous()
         rot = rot.reshape(3, 3).to(dev, torch.float32).contiguous()
         gt = gt.reshape(-1, 3).to(dev, torch.float32).contiguous()
@@ -74,6 +79,11 @@ class LossStage:
         if bg_ray is not None:
             bg_ray = bg_ray.reshape(R, 3).to(dev, torch.float32).contiguous()
             lp.bg_ray = bg_ray.data_ptr()
+        dmap = None
+        if depth is not None:
+            dmap = torch.empty(R, dtype=torch.float32, device=dev)
+            dp = _lib.LossDepth(depth.gt.data_ptr(), None if depth.mask is None else depth.mask.data_ptr(),
+                                depth.weight, dmap.data_ptr())
 
         def run(feat_t, conf_t):
             losses = torch.empty(_N_LOSS, dtype=torch.float32, device=dev)
@@ -81,11 +91,14 @@ class LossStage:
             mask = torch.empty(R, dtype=torch.int8, device=dev)
             dfeat = torch.zeros_like(feat_t)   # entries past the rays' samples (capacity padding) stay 0
             dconf = torch.zeros(n_points, dtype=torch.float32, device=dev) if conf_t.requires_grad else None
-            _lib.check(_lib.lib().sgn_loss_train(ctypes.byref(lp), _lib.ptr(campos), _lib.ptr(rot), R,
-                                                 ctypes.byref(q_abi), _lib.ptr(feat_t.detach()), _lib.ptr(gt),
-                                                 _lib.ptr(conf_t.detach()), _lib.ptr(full), _lib.ptr(mask),
-                                                 _lib.ptr(losses), _lib.ptr(dfeat), _lib.ptr(dconf), _lib.ptr(ws),
-                                                 ws.numel(), _lib.stream_handle()), "sgn_loss_train")
+            args = (_lib.ptr(campos), _lib.ptr(rot), R, ctypes.byref(q_abi), _lib.ptr(feat_t.detach()), _lib.ptr(gt),
+                    _lib.ptr(conf_t.detach()), _lib.ptr(full), _lib.ptr(mask), _lib.ptr(losses), _lib.ptr(dfeat),
+                    _lib.ptr(dconf), _lib.ptr(ws), ws.numel(), _lib.stream_handle())
+            if depth is None:
+                _lib.check(_lib.lib().sgn_loss_train(ctypes.byref(lp), *args), "sgn_loss_train")
+            else:
+                _lib.check(_lib.lib().sgn_loss_train_depth(ctypes.byref(lp), ctypes.byref(dp), *args),
+                           "sgn_loss_train_depth")
             return losses, full, mask, dfeat, None if dconf is None else dconf.view(conf_t.shape)
 
         losses, full, mask = _HipLoss.apply(feat, conf, run)
@@ -93,4 +106,8 @@ class LossStage:
         total = l_col + 3e-6 + zero_one_weight * l_zo
         parts = {"ray_masked_coarse_raycolor": l_col.detach(), "ray_miss_coarse_raycolor": losses[2].detach(),
                  "coarse_raycolor": losses[3].detach(), "conf_coefficient": l_zo.detach()}
-        return total, parts, full, mask.bool()
+        if depth is None:
+            return total, parts, full, mask.bool()
+        l_depth = losses[7].detach()   # its gradient is in d feat already
+        parts["coarse_depth"] = l_depth
+        return total + depth.weight * l_depth, parts, full, mask.bool(), dmap

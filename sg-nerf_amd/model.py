@@ -25,7 +25,9 @@ saveSemanticEmbedding / saveSemanticPoints / saveSemanticPoints_test
 (neural_points_volumetric_model.py:337-362, 674-720); checkpoints carry
 neural_points.points_feats / points_label / bpnet_points_embedding.  set_bg (plane background)
 returns the rays' bg_ray, which test() blends as T_bg * bg_ray and optimize_parameters composites
-into the loss the same way.  Pruning keeps the semantic
+into the loss the same way.  With opt.compute_depth (or depth_loss_items) test() also returns coarse_depth
+[1, R]; depth_loss_items = coarse_depth trains against inputs['gt_depth'] (masked by inputs['gt_mask'], else
+by gt_depth > 0) with loss_coarse_depth reported.  Pruning keeps the semantic
 per-point arrays aligned with the points (the reference leaves them unpruned).
 """
 import dataclasses
@@ -36,6 +38,7 @@ import torch
 
 from .opts import HotPathOpts
 from .ray_marching import NeuralPoints, NeuralPointsRayMarching
+from .train import depth_target
 from .weights import strip_prefix
 
 LOSS_NAMES = ["total", "ray_masked_coarse_raycolor", "ray_miss_coarse_raycolor", "coarse_raycolor",
@@ -217,7 +220,8 @@ class HipPointsVolumetricModel:
         npnt.points_conf = params.points_conf.detach().view(1, n, 1)
         self.optimizers = [self.trainer.opt_net, self.trainer.opt_pts]
         self.schedulers = []
-        self.loss_names = list(LOSS_NAMES)
+        # the depth loss is listed while depth supervision is on (base_rendering_model.py:611-618)
+        self.loss_names = list(LOSS_NAMES) + (["coarse_depth"] if self.opts.depth_loss_weight is not None else [])
 
     def init_scheduler(self, total_steps, opt):
         """iter_exponential_decay resumed at total_steps (the reference steps its schedulers that often)."""
@@ -350,6 +354,9 @@ class HipPointsVolumetricModel:
     def optimize_parameters(self, backward=True, total_steps=0):
         """neural_points_volumetric_model.py:320-331: forward, losses, backward, both Adam steps."""
         self._check_rotation(training=True)
+        w_d = self.opts.depth_loss_weight
+        if w_d is not None and self.input.get("gt_depth") is None:
+            raise ValueError("depth_loss_items is set: the batch needs gt_depth")
         if getattr(self, "trainer", None) is None:
             self.setup_optimizer(self.opt)
         if self.trainer is None:  # SG with predict_semantic: setup_optimizer waits for the embedding
@@ -374,14 +381,20 @@ class HipPointsVolumetricModel:
         # the plane background model's per-ray colour (set_bg -> inputs['bg_ray'], run/train_ft.py:209-218):
         # the loss composites T_bg * bg_ray + colour (neural_points_volumetric_model.py:175-177)
         bg_ray = inp.get("bg_ray")
+        # depth supervision (depth_loss_items = coarse_depth): inputs['gt_depth'] and, if present, inputs['gt_mask']
+        depth = None
+        if w_d is not None:
+            depth = depth_target(inp["gt_depth"], inp.get("gt_mask"), w_d, gt.shape[0], self.device)
         if backward:
-            parts, full, ray_mask = tr.step(*args, labels=labels, bg_ray=bg_ray)
+            parts, full, ray_mask, *dmap = tr.step(*args, labels=labels, bg_ray=bg_ray, depth=depth)
             self._weights_dirty = True
         else:
-            parts, full, ray_mask = tr.backward(*args, labels=labels, bg_ray=bg_ray)
+            parts, full, ray_mask, *dmap = tr.backward(*args, labels=labels, bg_ray=bg_ray, depth=depth)
         for k, v in parts.items():
             setattr(self, "loss_" + k, v)
         self.output = {"coarse_raycolor": full[None], "ray_mask": ray_mask[None].to(torch.int8)}
+        if dmap:
+            self.output["coarse_depth"] = dmap[0][None]
         self.coarse_raycolor = self.output["coarse_raycolor"]
         self.ray_mask = self.output["ray_mask"]
         self.update_rank_ray_miss(total_steps)   # neural_points_volumetric_model.py:328-330

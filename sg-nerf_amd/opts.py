@@ -78,6 +78,11 @@ class HotPathOpts:
     which_render_func: str = "radiance"
     which_blend_func: str = "alpha"
     bg_color: str = "white"
+    # depth (neural_points_volumetric_model.py:211, 620-624; base_rendering_model.py:611-618): compute_depth
+    # adds coarse_depth to the outputs, depth_loss_items = ("coarse_depth",) trains against inputs['gt_depth']
+    compute_depth: int = 0
+    depth_loss_items: Tuple[str, ...] = ()
+    depth_loss_weights: Tuple[float, ...] = (1.0,)
     # knobs of this implementation (no reference counterpart)
     # aggregator arithmetic: "f32" = the reference's fp32 products, each carried as three fp16 MFMA
     # products with fp32 accumulation (mlp_x3.hip); "f16" = fp16 MFMA operands (mlp.hip, faster)
@@ -100,6 +105,19 @@ class HotPathOpts:
               ("points_conf", self.conf_grad))
         return tuple(name for name, v in sw if v)
 
+    @property
+    def want_depth(self):
+        """Whether the outputs carry coarse_depth."""
+        return bool(self.compute_depth) or bool(self.depth_loss_items)
+
+    @property
+    def depth_loss_weight(self):
+        """The weight of the coarse_depth loss item, or None without depth supervision."""
+        if "coarse_depth" not in self.depth_loss_items:
+            return None
+        w = self.depth_loss_weights
+        return float(w[0] if len(w) == 1 else w[self.depth_loss_items.index("coarse_depth")])
+
     @classmethod
     def from_opt(cls, opt, **overrides):
         """Take every known field from a reference-style Namespace."""
@@ -109,6 +127,10 @@ class HotPathOpts:
                 v = getattr(opt, f.name)
                 if isinstance(v, list):
                     v = tuple(v)
+                if f.name in ("depth_loss_items", "depth_loss_weights"):   # unset (None) or one bare value
+                    if v is None:
+                        continue
+                    v = v if isinstance(v, tuple) else (v,)
                 kw[f.name] = v
         kw.update(overrides)
         o = cls(**kw)
@@ -151,6 +173,11 @@ class HotPathOpts:
             bad.append("inverse (disparity) ray generation is not implemented")
         if self.xyz_grad:
             bad.append("xyz_grad must be 0 (point positions feed the grid and the query, which carry no gradient)")
+        other = [i for i in self.depth_loss_items if i != "coarse_depth"]
+        if other:
+            bad.append(f"depth_loss_items: only coarse_depth is produced, not {', '.join(map(str, other))}")
+        if self.depth_loss_items and len(self.depth_loss_weights) not in (1, len(self.depth_loss_items)):
+            bad.append("depth_loss_weights must hold one weight or one per depth_loss_items entry")
         if bad:
             raise NotImplementedError("; ".join(bad))
         return self

@@ -203,6 +203,11 @@ def fill_invalid(output, input, bg_color=None):
     fq = torch.ones(B, OR, qs.shape[2], dtype=qs.dtype, device=dev)
     fq[0, keep] = qs[0]
     output["queried_shading"] = fq
+    if "coarse_depth" in output:   # [1, R''] -> [1, R], zeros (unmask's value; the reference expands nothing here)
+        d = output["coarse_depth"]
+        full = torch.zeros(B, OR, dtype=d.dtype, device=dev)
+        full[0, keep] = d[0]
+        output["coarse_depth"] = full
     if "ray_max_shading_opacity" in output:   # the opt.prob = 1 maps: unmask, zeros (:192-203)
         for name in PROBE_KEYS:
             t = output[name]
@@ -239,7 +244,11 @@ class NeuralPointsRayMarching:
     Hole probing (opt.prob = 1, :633-668): with `prob=1` (or, left None, `opt.prob` read at call time
     when the module was built from the driver's Namespace) both also return PROBE_KEYS, the per-ray
     maps run/train_ft.py's probe_hole reads; `query_size` overrides opts.query_size for that call
-    (probe_hole's prob_kernel_size).  With the switch off nothing changes: no key, no launch."""
+    (probe_hole's prob_kernel_size).  With the switch off nothing changes: no key, no launch.
+
+    Depth (opts.compute_depth, or depth_loss_items set): both also return coarse_depth -- [1, R''] compacted
+    from forward, [1, R] with zeros outside ray_mask from render / fill_invalid (:211, 620-624, as the reference
+    meant them: INTEGRATION.md section 1).  Without the options there is no such key."""
 
     def __init__(self, neural_points: NeuralPoints, aggregator_state, opt=None, device="cuda",
                  return_weights=True):
@@ -278,7 +287,7 @@ class NeuralPointsRayMarching:
         return self.renderer.render(campos, rot, raydir, near, far, want_opacity=True, want_blend=False,
                                     bg=bg, want_weights=want_weights, point_labels=pl, ray_labels=rl,
                                     seconds=inputs.get("seconds"), want_probe=want_probe,
-                                    query_size=query_size), raydir.shape[0]
+                                    query_size=query_size, want_depth=self.opts.want_depth), raydir.shape[0]
 
     def _weights(self, out, R):
         """weight [R,SR,K], blend_weight [R,SR,1], conf_coefficient [R,SR,K] (dense ray slots)."""
@@ -311,6 +320,8 @@ class NeuralPointsRayMarching:
         if self.return_weights:
             w, bw, cc = self._weights(out, R)
             res["weight"], res["blend_weight"], res["conf_coefficient"] = w[None], bw[None].clone(), cc[None]
+        if out.depth is not None:   # the kernel wrote 0 for the rays outside the mask
+            res["coarse_depth"] = out.depth[None].clone()
         if want_probe:   # sgn_probe wrote zero records for the rays outside the mask (unmask, :192-203)
             res.update(_probe_maps(out.probe))
         return res
@@ -330,6 +341,8 @@ class NeuralPointsRayMarching:
         if self.return_weights:
             w, bw, cc = self._weights(out, R)
             res["weight"], res["blend_weight"], res["conf_coefficient"] = w[keep][None], bw[keep][None], cc[keep][None]
+        if out.depth is not None:
+            res["coarse_depth"] = out.depth[keep][None]
         if want_probe:
             res.update(_probe_maps(out.probe[keep]))
         return res

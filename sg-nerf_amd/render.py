@@ -27,6 +27,7 @@ class RenderOut:
     wnorm: torch.Tensor = None    # [S_cap,8] normalised weight (when want_weights)
     blendw: torch.Tensor = None   # [R,SR] alpha-blend weight o*T (when want_weights)
     probe: torch.Tensor = None    # [R,48] packed hole-probing records (sgn_probe; when want_probe)
+    depth: torch.Tensor = None    # [R] coarse_depth, 0 for invalid rays (sgn_composite_depth; when want_depth)
 
 
 class PointTables:
@@ -128,6 +129,7 @@ class HipRenderer:
             self.wnorm = None
             self.blendw = None
             self.probe = None
+            self.depth = None
             self.viewdir = None   # [cap,3] rotated view direction per sample (rotated points only)
             self._cap = (R, cap)
         if self.points.rot is not None and self.viewdir is None:
@@ -182,7 +184,7 @@ class HipRenderer:
 
     def render(self, campos, camrotc2w, raydir, near, far, want_opacity=True, want_blend=False, marks=None,
                bg=None, want_weights=False, point_labels=None, ray_labels=None, seconds=None,
-               count_traffic=False, check_range="sync", want_probe=False, query_size=None):
+               count_traffic=False, check_range="sync", want_probe=False, query_size=None, want_depth=False):
         """One frame.  `marks(name)` (optional) is called between stages on the host thread
         (bench.py records HIP events on the current stream there).  `bg`: 3 floats
         overriding opts.bg_color.  `want_weights`: also produce the normalised neighbour
@@ -193,7 +195,9 @@ class HipRenderer:
         plain-fp32 path, sgn_aggregate_exact; "deferred" for pipelined frame loops + finish(), False).
         `want_probe`: also the per-ray hole-probing records (opt.prob = 1; sgn_probe, RenderOut.probe
         [R, 48]); implies want_opacity and want_blend.  `query_size`: overrides opts.query_size for this
-        call (probe_hole's prob_kernel_size); the cached grid is kept."""
+        call (probe_hole's prob_kernel_size); the cached grid is kept.  `want_depth`: also the depth map
+        (RenderOut.depth [R]: sum w z / (sum w + 1e-6) over the blend weights and the samples' camera-space z,
+        0 for rays without a valid sample; sgn_composite_depth in place of sgn_composite)."""
         o = self.opts
         if want_probe:
             want_opacity = want_blend = True
@@ -210,6 +214,8 @@ class HipRenderer:
             self.wnorm.zero_()
         if want_probe and self.probe is None:
             self.probe = torch.empty(max(self._cap[0], 1), _lib.PROBE_RECORD, dtype=torch.float32, device=self.device)
+        if want_depth and self.depth is None:
+            self.depth = torch.empty(max(self._cap[0], 1), dtype=torch.float32, device=self.device)
         mark("query")
         if o.semantic_guidance == 1 and (point_labels is None or ray_labels is None):
             raise ValueError("semantic_guidance = 1 needs point_labels and ray_labels")
@@ -287,12 +293,15 @@ class HipRenderer:
             cp.bg[i] = bg[i]
 
         def composite():
-            _lib.check(L.sgn_composite(ctypes.byref(cp), _lib.ptr(campos), _lib.ptr(rot), _lib.ptr(raydir), R,
-                                       _lib.ptr(q.t_table), q.per_ray_t, q.t_table.shape[-1], ctypes.byref(qo),
-                                       _lib.ptr(self.feat), _lib.ptr(self.rgb), _lib.ptr(self.mask), _lib.ptr(self.bgT),
-                                       _lib.ptr(self.opacity) if want_opacity else None,
-                                       _lib.ptr(self.blendw) if want_weights else None, _lib.stream_handle()),
-                       "sgn_composite")
+            args = (ctypes.byref(cp), _lib.ptr(campos), _lib.ptr(rot), _lib.ptr(raydir), R, _lib.ptr(q.t_table),
+                    q.per_ray_t, q.t_table.shape[-1], ctypes.byref(qo), _lib.ptr(self.feat), _lib.ptr(self.rgb),
+                    _lib.ptr(self.mask), _lib.ptr(self.bgT), _lib.ptr(self.opacity) if want_opacity else None,
+                    _lib.ptr(self.blendw) if want_weights else None)
+            if want_depth:
+                _lib.check(L.sgn_composite_depth(*args, _lib.ptr(self.depth), _lib.stream_handle()),
+                           "sgn_composite_depth")
+            else:
+                _lib.check(L.sgn_composite(*args, _lib.stream_handle()), "sgn_composite")
 
         def probe():
             # after the composite: reads its opacity and mask, and the aggregator's blend
@@ -308,7 +317,7 @@ class HipRenderer:
         self._range_check(check_range, lambda: (aggregate_exact(), composite(), probe()))
         return RenderOut(self.rgb[:R], self.mask[:R], self.bgT[:R], self.opacity[:R], q, self.feat, self.blend,
                          self.wnorm if want_weights else None, self.blendw[:R] if want_weights else None,
-                         self.probe[:R] if want_probe else None)
+                         self.probe[:R] if want_probe else None, self.depth[:R] if want_depth else None)
 
     def points_projected(self):
         """The last frame's projected point count and the neighbour indices >= n_points met so far

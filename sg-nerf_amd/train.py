@@ -30,6 +30,7 @@ oracle's query in the parity tests.
 """
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -192,16 +193,37 @@ def aggregate(points: PointParams, mlp: ViewMLP, campos, rot, raydir, samp_ray, 
     return feat, conf_coef, mask
 
 
+class DepthTarget(NamedTuple):
+    """Depth supervision of one batch (depth_loss_items = coarse_depth, base_rendering_model.py:611-618):
+    gt [R] fp32, mask [R] fp32 or None (then gt > 0), weight (depth_loss_weights[i])."""
+    gt: torch.Tensor
+    mask: Optional[torch.Tensor]
+    weight: float
+
+
+def depth_target(gt_depth, gt_mask, weight, R, device):
+    """inputs['gt_depth'] / inputs['gt_mask'] of any shape that reshapes to R -> DepthTarget on the device;
+    another length raises ValueError."""
+    def flat(t, name):
+        t = torch.as_tensor(t).to(device, torch.float32).reshape(-1).contiguous()
+        if t.numel() != R:
+            raise ValueError(f"{name} has {t.numel()} values, the batch {R} rays")
+        return t
+    return DepthTarget(flat(gt_depth, "gt_depth"), None if gt_mask is None else flat(gt_mask, "gt_mask"),
+                       float(weight))
+
+
 def loss_from_query(points, mlp, q, campos, rot, raydir, gt, opts: HotPathOpts, bg=(1.0, 1.0, 1.0),
-                    zero_one_weight=1e-4, zero_eps=1e-3):
+                    zero_one_weight=1e-4, zero_eps=1e-3, depth=None):
     """Reference losses for one batch given a sample-major query result q (dict of tensors:
     ray_ns [R], ray_soff [R], samp_ray [S], samp_locw [S,3], pidx [S,K]).
-    Returns (total loss, dict of parts, rendered colour [R,3], ray_mask [R])."""
+    Returns (total loss, dict of parts, rendered colour [R,3], ray_mask [R]) and, with `depth` (a
+    DepthTarget), the depth map [R] after them."""
     campos = campos.reshape(1, 3)
     rot = rot.reshape(3, 3)
     feat, conf_coef, mask = aggregate(points, mlp, campos, rot, raydir, q["samp_ray"], q["samp_locw"], q["pidx"])
     return composite_losses(points, q, feat, mask.sum(-1) > 0, campos, rot, raydir, gt, opts, bg, zero_one_weight,
-                            zero_eps)
+                            zero_eps, depth=depth)
 
 
 class _CumprodPositive(torch.autograd.Function):
@@ -223,14 +245,19 @@ class _CumprodPositive(torch.autograd.Function):
 
 
 def composite_losses(points, q, feat, valid, campos, rot, raydir, gt, opts: HotPathOpts, bg=(1.0, 1.0, 1.0),
-                     zero_one_weight=1e-4, zero_eps=1e-3, s_count=None):
+                     zero_one_weight=1e-4, zero_eps=1e-3, s_count=None, depth=None):
     """ray_dist + ray_march + the reference losses from per-sample features feat [S,4]
     (alpha, r, g, b) and the per-sample validity (>= 1 neighbour).  bg: a constant colour (3
     floats) or the rays' background [R, 3] (the plane model's bg_ray: T_bg * bg_ray + colour).
 
     s_count (device scalar, optional): only the first s_count of the S sample entries are
     real; the rest (capacity padding, for a graph-captured step with static shapes) are routed
-    to a sentinel ray row that is dropped, so the result equals the unpadded call."""
+    to a sentinel ray row that is dropped, so the result equals the unpadded call.
+
+    depth (a DepthTarget): depth supervision.  D = sum_s w_s z_s / (sum_s w_s + 1e-6) over the blend weights
+    w = o T and the samples' raw camera-space z (coarse_depth, neural_points_volumetric_model.py:620-624), 0 on
+    rays outside ray_mask; L = mean over all R rays of (m (D - gt))^2 is added with depth.weight and reported
+    as parts['coarse_depth']; the depth map [R] is returned as a fifth value."""
     R = raydir.shape[0]
     SR = opts.SR
     campos = campos.reshape(1, 3)
@@ -304,8 +331,17 @@ def composite_losses(points, q, feat, valid, campos, rot, raydir, gt, opts: HotP
     n_e = wr.sum() * (SR * K)
     l_zo = torch.sum((torch.log(val) + torch.log(1 - val)) * wr) / torch.clamp(n_e, min=1.0)
     total = l_col + 3e-6 + zero_one_weight * l_zo
-    return total, {"ray_masked_coarse_raycolor": l_col.detach(), "ray_miss_coarse_raycolor": l_miss,
-                   "coarse_raycolor": l_all, "conf_coefficient": l_zo.detach()}, full, ray_mask
+    parts = {"ray_masked_coarse_raycolor": l_col.detach(), "ray_miss_coarse_raycolor": l_miss,
+             "coarse_raycolor": l_all, "conf_coefficient": l_zo.detach()}
+    if depth is None:
+        return total, parts, full, ray_mask
+    w = o * acc
+    dmap = torch.where(ray_mask, (w * z).sum(-1) / (w.sum(-1) + 1e-6), torch.zeros((), device=dev))
+    g = depth.gt.reshape(R).to(dev, torch.float32)
+    m = (g > 0).to(g.dtype) if depth.mask is None else depth.mask.reshape(R).to(dev, torch.float32)
+    l_depth = torch.mean((m * (dmap - g)) ** 2)
+    parts["coarse_depth"] = l_depth.detach()
+    return total + depth.weight * l_depth, parts, full, ray_mask, dmap.detach()
 
 
 def _allreduce_buckets(grads, bucket_elems):
@@ -462,16 +498,17 @@ class Trainer:
             for g in opt.param_groups:
                 g["lr"] = base * f
 
-    def backward(self, campos, rot, raydir, near, far, gt, q=None, bg_ray=None):
+    def backward(self, campos, rot, raydir, near, far, gt, q=None, bg_ray=None, depth=None):
         """Forward + backward + gradient all-reduce (no parameter update).  bg_ray: the rays'
-        background [R, 3] (plane model) or None (white)."""
+        background [R, 3] (plane model) or None (white).  depth: a DepthTarget (depth supervision);
+        the depth map [R] is then returned as a fourth value."""
         if q is None:
             q = self._query(campos.reshape(3).contiguous(), raydir.reshape(-1, 3).contiguous(), near, far)
         self.opt_net.zero_grad(set_to_none=True)
         self.opt_pts.zero_grad(set_to_none=True)
         bg = (1.0, 1.0, 1.0) if bg_ray is None else bg_ray
-        total, parts, full, ray_mask = loss_from_query(self.points, self.mlp, q, campos, rot, raydir, gt, self.opts,
-                                                       bg)
+        total, parts, full, ray_mask, *dmap = loss_from_query(self.points, self.mlp, q, campos, rot, raydir, gt,
+                                                              self.opts, bg, depth=depth)
         total.backward()
         for p in self.point_params + self.net_params:
             if p.grad is None and p.requires_grad:
@@ -481,7 +518,7 @@ class Trainer:
         if trained:   # the sparse row exchange carries the trained tensors only
             _allreduce_point_rows(trained)
         parts["total"] = total.detach()
-        return parts, full.detach(), ray_mask
+        return (parts, full.detach(), ray_mask, *dmap)
 
     def apply(self):
         self._set_lr()
@@ -489,9 +526,9 @@ class Trainer:
         self.opt_pts.step()
         self.step_count += 1
 
-    def step(self, campos, rot, raydir, near, far, gt, q=None):
+    def step(self, campos, rot, raydir, near, far, gt, q=None, bg_ray=None, depth=None):
         """One optimisation step; returns the loss parts (detached) and the rendered colour."""
-        out = self.backward(campos, rot, raydir, near, far, gt, q)
+        out = self.backward(campos, rot, raydir, near, far, gt, q, bg_ray, depth)
         self.apply()
         return out
 

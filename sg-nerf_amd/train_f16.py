@@ -29,7 +29,7 @@ import torch.nn.functional as F
 from . import _lib
 from .flat_mlp import _colmap
 from .loss_hip import LossStage
-from .train import _pe, gather_counts, touched_rows
+from .train import DepthTarget, _pe, gather_counts, touched_rows
 from .train_f32 import ColourStage, _attach_bpack
 from .weights import BPNET
 
@@ -227,6 +227,7 @@ class F16Step:
         # ---- colour MLP + composite + losses ------------------------------------------------
         if graph:
             out = self._graph_losses(b, S, n)
+            b.depth_map = out.get("depth")
             total, parts, full, ray_mask = out["total"], dict(out["parts"]), out["full"], out["ray_mask"]
             dfs, dal, scale = out["dfs"], out["dal"], out["scale"]
         else:   # torch autograd, per sample / per ray
@@ -236,8 +237,10 @@ class F16Step:
             v = raydir[q.samp_ray[samp]]
             feat_s = torch.cat([alpha_t[:, None], self._colour(fs_t, v)], dim=-1)
             featS = torch.zeros(S, 4, device=dev).index_put((samp,), feat_s)
-            total, parts, full, ray_mask = self.loss_stage(tr.points, qo, featS, campos, rot, b.gt, o, R,
-                                                           bg_ray=b.bg_ray)
+            total, parts, full, ray_mask, *dmap = self.loss_stage(tr.points, qo, featS, campos, rot, b.gt, o, R,
+                                                                  bg_ray=b.bg_ray, depth=b.depth)
+            if dmap:
+                b.depth_map = dmap[0]
             total.backward()
             if n > 0:
                 dfs = fs_t.grad.contiguous()
@@ -279,7 +282,8 @@ class F16Step:
                                        _lib.ptr(col.vpe), stream), "sgn_colour_inputs")
         # hand-written colour MLP, losses and backward (train_f32.ColourStage), its weight gradients reduced
         st["amax"].zero_()
-        col.forward_and_loss(st["campos"], st["rot"], st["gt"], self.tr._loss_params(st["bg_ray"]), stream)
+        col.forward_and_loss(st["campos"], st["rot"], st["gt"], self.tr._loss_params(st["bg_ray"]), stream,
+                             st["depth"])
         col.backward(stream)
         _lib.check(L.sgn_reduce_partials(len(st["segs"]), st["segs"], stream), "sgn_reduce_partials")
         dfs = col.dfs
@@ -288,23 +292,31 @@ class F16Step:
         losses = col.losses
         total = losses[0] + 3e-6 + 1e-4 * losses[1]
         names = ["ray_masked_coarse_raycolor", "ray_miss_coarse_raycolor", "coarse_raycolor", "conf_coefficient"]
-        return {"scalars": torch.stack([total, losses[0], losses[2], losses[3], losses[1]]), "names": names,
+        scalars = [total, losses[0], losses[2], losses[3], losses[1]]
+        if st["depth"] is not None:
+            scalars[0] = total + st["depth"].weight * losses[7]
+            scalars.append(losses[7])
+            names.append("coarse_depth")
+        return {"scalars": torch.stack(scalars), "names": names,
                 "full": col.full[:st["R"]], "ray_mask": col.mask[:st["R"]], "dfs": dfs, "dal": dal, "scale": scale}
 
     def _graph_losses(self, b, S, n):
         """Replay the captured loss stage for this step's capacity bucket (item / sample counts
         rounded up to GRAPH_BUCKET); captured on first use and again when a buffer it reads
         moved.  At most GRAPH_CACHE graphs are kept.  A step with a per-ray background (bg_ray)
-        replays a graph of its own whose static bg_ray buffer the step's colours are copied into."""
+        replays a graph of its own whose static bg_ray buffer the step's colours are copied into; so does a
+        step with depth supervision (static gt_depth / gt_mask buffers; the weight and the mask's presence
+        are part of the key: the captured launch holds them)."""
         tr, dev = self.tr, self.device
-        q, R, campos, rot, raydir, gt, bg_ray = b.q, b.R, b.campos, b.rot, b.raydir, b.gt, b.bg_ray
+        q, R, campos, rot, raydir, gt, bg_ray, depth = b.q, b.R, b.campos, b.rot, b.raydir, b.gt, b.bg_ray, b.depth
         P, fl = tr.points, tr.mlp.flat
         cap = R * tr.opts.SR
         Sc = min(cap, -(-max(S, 1) // GRAPH_BUCKET) * GRAPH_BUCKET)
         Nc = min(Sc, -(-max(n, 1) // GRAPH_BUCKET) * GRAPH_BUCKET)
         key = (R, Sc, Nc, q.work.data_ptr(), q.counters.data_ptr(), self.fs.data_ptr(), self.feat.data_ptr(),
                fl.data_ptr(), fl.grad.data_ptr(), P.points_conf.data_ptr(),
-               None if P.points_conf.grad is None else P.points_conf.grad.data_ptr(), bg_ray is not None)
+               None if P.points_conf.grad is None else P.points_conf.grad.data_ptr(), bg_ray is not None,
+               None if depth is None else (depth.mask is not None, depth.weight))
         st = self._graphs.pop(key, None)
         if st is not None:
             self._graphs[key] = st              # most recently used goes last (LRU eviction order)
@@ -316,6 +328,8 @@ class F16Step:
             st = {"key": key, "R": R, "Sc": Sc, "Nc": Nc, "q": q,
                   "raydir": raydir.clone(), "gt": gt.clone(), "campos": campos.clone(), "rot": rot.clone(),
                   "bg_ray": None if bg_ray is None else bg_ray.clone(),
+                  "depth": None if depth is None else DepthTarget(
+                      depth.gt.clone(), None if depth.mask is None else depth.mask.clone(), depth.weight),
                   "fs32": torch.zeros(Nc, 256, **f32), "al32": torch.zeros(Nc, **f32),
                   "v": torch.zeros(Nc, 3, **f32), "samp": torch.zeros(Nc, dtype=torch.int32, device=dev),
                   "amax": torch.zeros(4, dtype=torch.int32, device=dev)}
@@ -326,6 +340,8 @@ class F16Step:
             col = st["col"] = ColourStage(tr, q.abi(), R, Nc, q.counters[1:2].data_ptr(), st["fs32"], None, self.feat,
                                           torch.zeros(self.feat.shape[0] + 1, 4, **f32), st["amax"], products=1,
                                           zero_dfs=True)
+            if depth is not None:
+                col.depth = torch.empty(max(R, 1), **f32)
             st["segs"] = (_lib.PartialSegment * len(col.segments))(*col.segments)
             st["bpack"] = _attach_bpack(col.gemms, dev)
             cg = P.points_conf.grad   # None: conf is frozen, the stage writes no d conf
@@ -356,19 +372,24 @@ class F16Step:
             self._graphs[key] = st
         # the step's inputs into the graph's static buffers: one launch
         _lib.copy_segments([(raydir, st["raydir"]), (gt, st["gt"]), (campos, st["campos"]), (rot, st["rot"])] +
-                           ([] if bg_ray is None else [(bg_ray, st["bg_ray"])]))
+                           ([] if bg_ray is None else [(bg_ray, st["bg_ray"])]) +
+                           ([] if depth is None else [(depth.gt, st["depth"].gt)]) +
+                           ([] if depth is None or depth.mask is None else [(depth.mask, st["depth"].mask)]))
         st["graph"].replay()
         out = st["out"]
         # the loss, its parts, the rendered colour and the ray mask out of the graph's buffers: one
         # launch into one fresh allocation (the caller may keep them across steps)
         nsc = out["scalars"].numel()
         o_full = 8 * (-(-nsc // 8))
-        buf = torch.empty(o_full + 3 * R + -(-R // 4), dtype=torch.float32, device=dev)
+        nm = -(-R // 4)
+        buf = torch.empty(o_full + 3 * R + nm + (R if depth is not None else 0), dtype=torch.float32, device=dev)
         sc, full = buf[:nsc], buf[o_full:o_full + 3 * R].view(R, 3)
-        ray_mask = buf[o_full + 3 * R:].view(torch.bool)[:R]
-        _lib.copy_segments([(out["scalars"], sc), (out["full"], full), (out["ray_mask"], ray_mask)])
+        ray_mask = buf[o_full + 3 * R:o_full + 3 * R + nm].view(torch.bool)[:R]
+        dmap = buf[o_full + 3 * R + nm:] if depth is not None else None
+        _lib.copy_segments([(out["scalars"], sc), (out["full"], full), (out["ray_mask"], ray_mask)] +
+                           ([] if depth is None else [(st["col"].depth[:R], dmap)]))
         return {"total": sc[0], "parts": {k: sc[1 + i] for i, k in enumerate(out["names"])},
-                "full": full, "ray_mask": ray_mask,
+                "full": full, "ray_mask": ray_mask, "depth": dmap,
                 "dfs": out["dfs"], "dal": out["dal"], "scale": out["scale"]}
 
     # -- weight gradients of the row layers ---------------------------------------------------

@@ -158,8 +158,10 @@ class ColourStage:
         self.losses = torch.zeros(8, **f32)
         self.full = torch.empty(max(R, 1), 3, **f32)
         self.mask = torch.empty(max(R, 1), dtype=torch.int8, device=dev)
-        self.loss_ws = torch.empty(max(int(L.sgn_loss_workspace_bytes(R, trainer.opts.SR)), 16), dtype=torch.uint8,
-                                   device=dev)
+        # sized for the depth-supervised stage too (R floats and a few partial sums more)
+        self.loss_ws = torch.empty(max(int(L.sgn_loss_depth_workspace_bytes(R, trainer.opts.SR)), 16),
+                                   dtype=torch.uint8, device=dev)
+        self.depth = None   # [R] the depth map, allocated by the first depth-supervised step
         self.part_col = [torch.empty(SPLITS_ITEMS, 128, n, **f32) for n in (129, 129, 281)]
         self.part_c6 = torch.empty(int(L.sgn_train_head_partial_floats(0)), **f32)
         # ---- the launch arguments (pointers of persistent buffers: built once) ------------------
@@ -210,9 +212,11 @@ class ColourStage:
                                    128, 128)]
         self.w6, self.b6 = W("color_branch.6")[0], A.B("color_branch.6")
 
-    def forward_and_loss(self, campos, rot, gt, lp, st):
+    def forward_and_loss(self, campos, rot, gt, lp, st, depth=None):
         """Colour forward into feat[.].yzw, then the losses, on stream st: the loss vector (sgn_loss_train's
-        8 floats), full [R, 3] and mask [R] (int8) land in self.losses / full / mask, d feat in self.dfeat."""
+        8 floats), full [R, 3] and mask [R] (int8) land in self.losses / full / mask, d feat in self.dfeat.
+        depth (a train.DepthTarget): sgn_loss_train_depth instead -- L_depth in losses[7], the depth map in
+        self.depth, d feat with the depth term."""
         L = _lib.lib()
         ck, p = _lib.check, _lib.ptr
         P = self.points
@@ -220,9 +224,17 @@ class ColourStage:
             ck(L.sgn_x3_gemm(ctypes.byref(gs), st), "sgn_x3_gemm")
         ck(L.sgn_train_colour_head(ctypes.byref(self.qo), self.n_items, p(self.h[2]), self.w6, self.b6, p(self.feat),
                                    st), "sgn_train_colour_head")
-        ck(L.sgn_loss_train(ctypes.byref(lp), p(campos), p(rot), self.R, ctypes.byref(self.qo), p(self.feat), p(gt),
-                            p(P.points_conf), p(self.full), p(self.mask), p(self.losses), p(self.dfeat),
-                            p(P.points_conf.grad), p(self.loss_ws), self.loss_ws.numel(), st), "sgn_loss_train")
+        args = (p(campos), p(rot), self.R, ctypes.byref(self.qo), p(self.feat), p(gt), p(P.points_conf), p(self.full),
+                p(self.mask), p(self.losses), p(self.dfeat), p(P.points_conf.grad), p(self.loss_ws),
+                self.loss_ws.numel(), st)
+        if depth is None:
+            ck(L.sgn_loss_train(ctypes.byref(lp), *args), "sgn_loss_train")
+            return
+        if self.depth is None:
+            self.depth = torch.empty(max(self.R, 1), dtype=torch.float32, device=self.full.device)
+        dp = _lib.LossDepth(depth.gt.data_ptr(), None if depth.mask is None else depth.mask.data_ptr(), depth.weight,
+                            self.depth.data_ptr())
+        ck(L.sgn_loss_train_depth(ctypes.byref(lp), ctypes.byref(dp), *args), "sgn_loss_train_depth")
 
     def backward(self, st):
         """d feat -> d f_s (self.dfs) and the colour layers' weight-gradient partials, on stream st."""
@@ -367,10 +379,11 @@ class F32Step:
                                    A.flat.device)
 
     # -- one step ------------------------------------------------------------------------------
-    def run(self, pt, proj, blob, campos, rot, gt, lp):
+    def run(self, pt, proj, blob, campos, rot, gt, lp, depth=None):
         """Forward + backward of one batch after the query (gradients added into flat.grad and the
         point gradients; those must be zero / as the caller wants them).  Returns the device loss
-        vector (sgn_loss_train's 8 floats), the rendered colour [R, 3] and the ray mask [R] (int8)."""
+        vector (sgn_loss_train's 8 floats), the rendered colour [R, 3] and the ray mask [R] (int8);
+        with depth (a train.DepthTarget) the depth map is in self.colour.depth."""
         L = _lib.lib()
         st = _lib.stream_handle()
         tr, K, qo, col = self.trainer, self.K, self.qo, self.colour
@@ -393,7 +406,7 @@ class F32Step:
         if self.D:
             ck(L.sgn_train_row_gather(ctypes.byref(qo), K, p(self.row_off), p(self.counts), p(tr.bpnet32), self.D,
                                       p(self.bprow), st), "sgn_train_row_gather")
-        col.forward_and_loss(campos, rot, gt, lp, st)
+        col.forward_and_loss(campos, rot, gt, lp, st, depth)
         col.backward(st)
         gemm(self.g_z4)
         ck(L.sgn_train_row_head(ctypes.byref(pt), ctypes.byref(qo), K, p(self.row_off), p(self.counts), p(self.z[3]),
@@ -463,16 +476,25 @@ class F32Runner:
         key = (R, q.work.data_ptr(), q.pidx.data_ptr(), fl.data_ptr(), fl.grad.data_ptr())
         if self.key != key:
             self.step, self.key = F32Step(tr, q, R), key
-        losses, full, mask = self.step.run(pt, self.proj, self._blob, b.campos, b.rot, b.gt, tr._loss_params(b.bg_ray))
+        losses, full, mask = self.step.run(pt, self.proj, self._blob, b.campos, b.rot, b.gt, tr._loss_params(b.bg_ray),
+                                           b.depth)
         # the step's buffers are reused by the next step: the losses, the colour and the mask out into
         # one fresh allocation (one launch), as the f16 step's graph outputs
         nl = losses.numel()
-        buf = torch.empty(nl + 3 * R + -(-R // 4), dtype=torch.float32, device=dev)
+        nm = -(-R // 4)
+        buf = torch.empty(nl + 3 * R + nm + (R if b.depth is not None else 0), dtype=torch.float32, device=dev)
         lo, full_o = buf[:nl], buf[nl:nl + 3 * R].view(R, 3)
-        mask_o = buf[nl + 3 * R:].view(torch.int8)[:R]
-        _lib.copy_segments([(losses, lo), (full, full_o), (mask, mask_o)])
+        mask_o = buf[nl + 3 * R:nl + 3 * R + nm].view(torch.int8)[:R]
+        segs = [(losses, lo), (full, full_o), (mask, mask_o)]
+        if b.depth is not None:
+            b.depth_map = buf[nl + 3 * R + nm:]
+            segs.append((self.step.colour.depth[:R], b.depth_map))
+        _lib.copy_segments(segs)
         parts = {"ray_masked_coarse_raycolor": lo[0], "ray_miss_coarse_raycolor": lo[2],
                  "coarse_raycolor": lo[3], "conf_coefficient": lo[1], "total": lo[0] + 3e-6 + 1e-4 * lo[1]}
+        if b.depth is not None:
+            parts["coarse_depth"] = lo[7]
+            parts["total"] = parts["total"] + b.depth.weight * lo[7]
         return parts, full_o, mask_o
 
     def dp_rows(self):

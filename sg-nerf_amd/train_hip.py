@@ -25,7 +25,9 @@ fp32 accumulation, train_f16.F16Step: one host sync per step, the loss stage as 
 `apply` steps the two Adam groups (lr 5e-4 / plr 2e-3, iter_exponential_decay): the MLP's on
 sgn_adam_step_multi, the points' on the row-sparse exact sgn_adam_rows (PointAdam(rows=True):
 bit-identical to the dense update, applied at the next step's launch or at a flush).  The plane
-background model's per-ray colour (inputs['bg_ray']) enters the loss stage as T_bg * bg_ray.
+background model's per-ray colour (inputs['bg_ray']) enters the loss stage as T_bg * bg_ray.  Depth
+supervision (`depth=`, a train.DepthTarget) switches the loss stage to sgn_loss_train_depth on every path;
+without it the stock entry runs as before.
 
 Which point tensors train follows opts.feat_grad / color_grad / dir_grad / conf_grad (neural_points.py:410-416):
 a frozen tensor's gradient pointer is NULL at the C ABI (no kernel computes it), it is in no point-Adam group
@@ -40,7 +42,7 @@ from . import _lib
 from .flat_mlp import FlatMLP, _Packer, _PackerF32  # noqa: F401  (re-exported)
 from .opts import HotPathOpts
 from .point_adam import NoPointAdam, PointAdam
-from .train import PointParams, _allreduce_buckets, _allreduce_point_rows
+from .train import PointParams, _allreduce_buckets, _allreduce_point_rows, depth_target
 from .weights import layers_for
 
 
@@ -262,12 +264,14 @@ class HipTrainer:
             lp.bg_ray = bg_ray.data_ptr()
         return lp
 
-    def backward(self, campos, rot, raydir, near, far, gt, labels=None, bg_ray=None):
+    def backward(self, campos, rot, raydir, near, far, gt, labels=None, bg_ray=None, depth=None):
         """Forward + backward + gradient all-reduce (no parameter update).  labels: (point_labels,
         ray_labels, seconds) for the semantic-guided query (semantic_guidance = 1).  bg_ray: the
         rays' background [1, R, 3] of the plane background model (inputs['bg_ray']): the composite
         and its gradient use T_bg * bg_ray per ray (neural_points_volumetric_model.py:175-177).
-        Returns (loss parts, rendered colour [R,3], ray_mask [R])."""
+        depth: a train.DepthTarget (depth_loss_items = coarse_depth): the loss stage runs sgn_loss_train_depth,
+        parts carry coarse_depth and its weighted term is in total.
+        Returns (loss parts, rendered colour [R,3], ray_mask [R]) and, with depth, the depth map [R]."""
         dev = self.device
         campos = campos.reshape(3).to(dev, torch.float32).contiguous()
         rot = rot.reshape(3, 3).to(dev, torch.float32).contiguous()
@@ -277,7 +281,10 @@ class HipTrainer:
         bg_ray = self._bg_ray(bg_ray, R)
         q = self._last_q = self._query(campos, raydir, near, far, labels)
         dp = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        b = SimpleNamespace(campos=campos, rot=rot, raydir=raydir, gt=gt, R=R, bg_ray=bg_ray, q=q, dp=dp)
+        if depth is not None:
+            depth = depth_target(depth.gt, depth.mask, depth.weight, R, dev)
+        b = SimpleNamespace(campos=campos, rot=rot, raydir=raydir, gt=gt, R=R, bg_ray=bg_ray, q=q, dp=dp, depth=depth,
+                            depth_map=None)
         step = self.stepper
         step.begin(b)
         # the gradients are made ready after the point Adam's launch: it applies a deferred step, which
@@ -292,6 +299,8 @@ class HipTrainer:
         self.allreduce_grads([self.mlp.flat])
         if dp and self.point_params:   # the sparse row exchange carries the trained tensors only
             self._adam_union(_allreduce_point_rows([p.grad for p in self.point_params], *step.dp_rows()))
+        if depth is not None:
+            return parts, full, ray_mask.bool(), b.depth_map
         return parts, full, ray_mask.bool()
 
     @property
@@ -321,8 +330,8 @@ class HipTrainer:
                                 for o in (self.opt_net, self.opt_pts))
         self.step_count += 1
 
-    def step(self, campos, rot, raydir, near, far, gt, labels=None, bg_ray=None):
-        out = self.backward(campos, rot, raydir, near, far, gt, labels, bg_ray)
+    def step(self, campos, rot, raydir, near, far, gt, labels=None, bg_ray=None, depth=None):
+        out = self.backward(campos, rot, raydir, near, far, gt, labels, bg_ray, depth)
         self.apply()
         return out
 
