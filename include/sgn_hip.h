@@ -694,6 +694,26 @@ int sgn_composite_depth(const sgn_composite_params *cp, const float *d_campos, c
                         int8_t *d_out_mask, float *d_out_bgT, float *d_out_opacity, float *d_out_blendw,
                         float *d_out_depth, sgn_stream_t stream);
 
+/* Early ray termination, one tier (no reference counterpart): the work list of the slot range [lo, hi),
+ * 0 <= lo < hi <= SR, lo < SR, for the rays that still transmit more than eps (0 <= eps < 1).  One thread
+ * per ray recomputes the transmittance T over the closed slots [0, lo) from d_feat with sgn_composite's
+ * arithmetic, operation for operation (lo = 0: T = 1, every ray is live), then for the ray's samples
+ * ray_soff[r] + s, lo <= s < min(hi, ray_ns[r]), with samp_nnb > 0:
+ *   T >  eps  (live)     the ids are appended to d_work_out (int32[S_capacity], unordered)
+ *   T <= eps  (finished) d_feat[id] = (0, 0, 0, 0) -- alpha 0, so the composite gives the sample opacity
+ *                        exactly 0 and a transmittance factor of 1.0f, and the ray stays finished in every
+ *                        later call -- and d_stop_slot[r] = lo if it still holds SR (int32[R], pre-filled
+ *                        with SR by the caller: the boundary at which the ray was first found finished)
+ * d_counters_out int32[4], cleared by the call: [0] = q->counters[0], [1] = ids appended, [2] = valid
+ * samples skipped so far (this call's plus d_counters_prev[2], the previous tier's counters, or NULL),
+ * [3] = 0.  The aggregators take a copy of q with work = d_work_out and counters = d_counters_out.
+ * d_feat 16-B aligned; the slots [0, lo) of every ray must hold this frame's features (aggregated or
+ * zeroed by an earlier tier).  One launch, no host synchronisation. */
+int sgn_early_stop_tier(const sgn_composite_params *cp, const float *d_campos, const float *d_camrotc2w,
+                        int64_t R, const sgn_query_out *q, float *d_feat, int32_t lo, int32_t hi, float eps,
+                        int64_t S_capacity, int32_t *d_work_out, int32_t *d_counters_out,
+                        const int32_t *d_counters_prev, int32_t *d_stop_slot, sgn_stream_t stream);
+
 /* ray_march on dense [R, SR] inputs (diff_ray_marching.py:509-555, alpha blend +
  * radiance render): ray_dist/valid/feat(float4) in, rgb[R*3] (+ bg*T if bg != NULL,
  * host pointer to 3 floats), opacity/acc_transmission/blend_weight[R*SR], bg T[R]. */

@@ -205,6 +205,8 @@ SIGNATURES = {
                               c_i32, ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgn_composite_depth": (c_i32, [ctypes.POINTER(CompositeParams), c_vp, c_vp, c_vp, c_i64, c_vp, c_i32,
                                     c_i32, ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgn_early_stop_tier": (c_i32, [ctypes.POINTER(CompositeParams), c_vp, c_vp, c_i64, ctypes.POINTER(QueryOut), c_vp,
+                                    c_i32, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgn_probe": (c_i32, [ctypes.POINTER(PointTables), ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_i64, c_i32, c_i32,
                           c_vp, c_vp]),
     "sgn_loss_workspace_bytes": (c_sz, [c_i64, c_i32]),

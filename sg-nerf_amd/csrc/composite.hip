@@ -264,3 +264,126 @@ extern "C" int sgn_composite_depth(const sgn_composite_params *cp, const float *
     return sgn::composite_launch<true>(cp, d_campos, d_camrotc2w, d_raydir, R, q, d_feat, d_out_rgb, d_out_mask,
                                        d_out_bgT, d_out_opacity, d_out_blendw, d_out_depth, stream);
 }
+
+// ---- early ray termination: one tier's work list (sgn_early_stop_tier) ---------------------
+namespace sgn {
+namespace {
+
+struct TierArgs {
+    const float *campos, *rot;
+    const int32_t *ray_ns, *ray_soff, *samp_nnb;
+    const float *samp_locw;
+    float *feat;
+    const int32_t *q_counters, *prev;
+    int64_t R, cap;
+    int SR, unit, lo, hi;
+    float vz, eps;
+    int32_t *work, *counters, *stop_slot;
+};
+
+constexpr int TIER_TPB = 256;
+
+// One thread per ray.  T over the closed slots [0, lo) is k_composite's arithmetic, operation for
+// operation (pers_z, running cummax, the distance replacement, o = 1 - expf(-sigma dist),
+// T *= 1 - o + 1e-10f; a slot >= ray_ns is padding, whose factor rounds to 1.0f), so the ray this
+// kernel finishes is a ray whose composite reaches slot lo with that same T.  lo < SR: no closed slot
+// is a full ray's last one (interval vsize_z).  A live ray's valid samples of [lo, hi) go to the work
+// list -- the wave's counts are scanned and one lane draws the wave's range with one atomic -- a
+// finished ray's get feat 0 (alpha 0: opacity exactly 0, transmittance factor 1.0f).
+__global__ __launch_bounds__(TIER_TPB) void k_early_stop_tier(TierArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * TIER_TPB + threadIdx.x;
+    const bool in = r < a.R;
+    int ns = in ? a.ray_ns[r] : 0;
+    ns = ns < a.SR ? ns : a.SR;
+    const int off = in ? a.ray_soff[r] : 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.counters[0] = a.q_counters[0];
+        if (a.prev) atomicAdd(a.counters + 2, a.prev[2]);
+    }
+    float T = 1.f;
+    const int nclose = a.lo < ns ? a.lo : ns;
+    if (nclose > 0) {
+        const float z0 = pers_z(a.campos, a.rot, 0.f, 0.f, 0.f);
+        auto z_at = [&](int s) {
+            if (s >= ns) return z0;
+            const int64_t id = off + s;
+            return pers_z(a.campos, a.rot, a.samp_locw[id * 3], a.samp_locw[id * 3 + 1], a.samp_locw[id * 3 + 2]);
+        };
+        float prev_cm = z_at(0);
+        for (int s = 0; s < nclose; ++s) {  // slot s: the interval up to slot s + 1's cummax
+            const float cm = fmaxf(prev_cm, z_at(s + 1));
+            float dist = cm - prev_cm;
+            const int64_t id = off + s;
+            const bool v = a.samp_nnb[id] > 0;
+            const bool mask = dist < 1e-8f || (a.unit && dist > 2.f * a.vz);
+            dist = mask ? a.vz : dist;
+            const float valid = v ? 1.f : 0.f;
+            dist = dist * valid;
+            const float sigma = (v ? a.feat[id * 4] : 0.f) * valid;
+            const float o = 1.f - expf(-sigma * dist);
+            T = T * (1.f - o + 1e-10f);
+            prev_cm = cm;
+        }
+    }
+    const bool fin = in && T <= a.eps;
+    if (fin && a.stop_slot[r] == a.SR) a.stop_slot[r] = a.lo;
+    const int s1 = a.hi < ns ? a.hi : ns;
+    int cnt = 0;
+    for (int s = a.lo; s < s1; ++s) cnt += a.samp_nnb[off + s] > 0 ? 1 : 0;
+    const int emit = fin ? 0 : cnt;
+    int incl = emit, skip = fin ? cnt : 0;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+        skip += __shfl_xor(skip, d);
+    }
+    const int total = __shfl(incl, 63);
+    int base = 0;
+    if (lane == 63 && total > 0) base = atomicAdd(a.counters + 1, total);
+    base = __shfl(base, 63);
+    if (lane == 0 && skip > 0) atomicAdd(a.counters + 2, skip);
+    int64_t w = (int64_t)base + incl - emit;
+    for (int s = a.lo; s < s1; ++s) {
+        const int id = off + s;
+        if (a.samp_nnb[id] <= 0) continue;
+        if (fin) {
+            *(float4 *)(a.feat + (int64_t)id * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            if (w < a.cap) a.work[w] = id;
+            ++w;
+        }
+    }
+}
+
+}  // namespace
+}  // namespace sgn
+
+extern "C" int sgn_early_stop_tier(const sgn_composite_params *cp, const float *d_campos, const float *d_camrotc2w,
+                                   int64_t R, const sgn_query_out *q, float *d_feat, int32_t lo, int32_t hi, float eps,
+                                   int64_t S_capacity, int32_t *d_work_out, int32_t *d_counters_out,
+                                   const int32_t *d_counters_prev, int32_t *d_stop_slot, sgn_stream_t stream) {
+    using namespace sgn;
+    SGN_REQUIRE(cp && d_campos && d_camrotc2w && q && d_feat && d_work_out && d_counters_out && d_stop_slot,
+                "null argument");
+    SGN_REQUIRE(q->ray_ns && q->ray_soff && q->samp_nnb && q->samp_locw && q->counters,
+                "query outputs (ray_ns, ray_soff, samp_nnb, samp_locw, counters) required");
+    SGN_REQUIRE(cp->SR > 0, "SR must be positive");
+    SGN_REQUIRE(0 <= lo && lo < hi && hi <= cp->SR && lo < cp->SR, "slot range must satisfy 0 <= lo < hi <= SR");
+    SGN_REQUIRE(eps >= 0.f && eps < 1.f, "eps must satisfy 0 <= eps < 1");
+    SGN_REQUIRE(R >= 0 && S_capacity >= 0 && S_capacity < ((int64_t)1 << 31), "R / S_capacity out of range");
+    SGN_REQUIRE(((uintptr_t)d_feat & 15) == 0, "16-byte aligned feat required");
+    hipStream_t st = as_stream(stream);
+    SGN_CHECK_HIP(hipMemsetAsync(d_counters_out, 0, 4 * sizeof(int32_t), st));
+    TierArgs a;
+    a.campos = d_campos; a.rot = d_camrotc2w;
+    a.ray_ns = q->ray_ns; a.ray_soff = q->ray_soff; a.samp_nnb = q->samp_nnb; a.samp_locw = q->samp_locw;
+    a.feat = d_feat; a.q_counters = q->counters; a.prev = d_counters_prev;
+    a.R = R; a.cap = S_capacity; a.SR = cp->SR; a.unit = cp->raydist_mode_unit; a.lo = lo; a.hi = hi;
+    a.vz = cp->vsize_z; a.eps = eps;
+    a.work = d_work_out; a.counters = d_counters_out; a.stop_slot = d_stop_slot;
+    const int64_t blocks = R > 0 ? (R + TIER_TPB - 1) / TIER_TPB : 1;  // one block at least: counters[0]
+    hipLaunchKernelGGL(k_early_stop_tier, dim3((unsigned)blocks), dim3(TIER_TPB), 0, st, a);
+    SGN_CHECK_HIP(hipGetLastError());
+    return 0;
+}

@@ -72,10 +72,20 @@ class HipPointsVolumetricModel:
                             help="1: do not reproduce the voxel_idx>0 grid bug (worldcoords.py:395)")
         parser.add_argument("--sgn_reservoir_seed", type=int, default=0,
                             help="seed of the per-voxel reservoir (the reference uses the wall clock)")
+        parser.add_argument("--sgn_early_stop", type=float, default=0.0,
+                            help="early ray termination of test renders: transmittance threshold, 0 = off")
+        parser.add_argument("--sgn_early_stop_slots", type=str, default="4,8,16",
+                            help="slot boundaries at which early ray termination looks at the transmittance")
         return parser
 
     def name(self):
         return self.__class__.__name__
+
+    @property
+    def _return_weights(self):
+        """The per-slot weight outputs (weight, blend_weight, conf_coefficient) need every sample aggregated,
+        so a model run with early ray termination (sgn_early_stop > 0) renders without them."""
+        return not self.opts.early_stop > 0
 
     # -- BaseModel.initialize / setup -------------------------------------------------
     def initialize(self, opt):
@@ -89,6 +99,10 @@ class HipPointsVolumetricModel:
             extra["fix_occ0"] = int(opt.sgn_fix_occ0)
         if hasattr(opt, "sgn_reservoir_seed"):
             extra["reservoir_seed"] = int(opt.sgn_reservoir_seed)
+        if hasattr(opt, "sgn_early_stop"):
+            extra["early_stop"] = float(opt.sgn_early_stop)
+        if hasattr(opt, "sgn_early_stop_slots"):
+            extra["early_stop_slots"] = tuple(int(x) for x in str(opt.sgn_early_stop_slots).replace(",", " ").split())
         # rendering (test / probe) runs the test-mode depth table; the trainer jitters (is_train)
         self.opts = HotPathOpts.from_opt(opt, **extra, is_train=0).check_supported()
         self.model_names = ["ray_marching"]
@@ -160,7 +174,7 @@ class HipPointsVolumetricModel:
             if aggregator_state is None:
                 raise ValueError("set_points: aggregator_state required before the first render")
             self.net_ray_marching = NeuralPointsRayMarching(self.neural_points, aggregator_state, self.opts,
-                                                            self.device)
+                                                            self.device, return_weights=self._return_weights)
         else:
             self._sync_weights()
             self.net_ray_marching.neural_points = self.neural_points
@@ -517,5 +531,6 @@ class HipPointsVolumetricModel:
         sd = torch.load(path, map_location="cpu", weights_only=True)
         self.neural_points = NeuralPoints.from_state_dict(sd, self.device)
         self._check_rotation()
-        self.net_ray_marching = NeuralPointsRayMarching(self.neural_points, strip_prefix(sd), self.opts, self.device)
+        self.net_ray_marching = NeuralPointsRayMarching(self.neural_points, strip_prefix(sd), self.opts, self.device,
+                                                        return_weights=self._return_weights)
         return path

@@ -7,6 +7,7 @@ models/neural_points_volumetric_model.py:63-124).  Defaults below are the
 ScanNet values of dev_scripts/w_scannet_etf/scene241.sh:11-106 and
 pointnerf/run/checkpoints/scannet/scene0710_00640480/opt.txt.
 """
+import numbers
 from dataclasses import dataclass, field, fields, replace
 from typing import Tuple
 
@@ -89,6 +90,11 @@ class HotPathOpts:
     precision: str = "f32"
     fix_occ0: int = 0          # 1: do not reproduce the `voxel_idx > 0` bug (worldcoords.py:395)
     reservoir_seed: int = 0    # replaces the reference's wall-clock curand seed (:314, :402)
+    # early ray termination of HipRenderer.render (render.py): a ray whose transmittance has fallen to
+    # early_stop or below at a slot boundary of early_stop_slots skips its remaining samples; a colour
+    # channel moves by at most 1.001 * early_stop.  0 = off (every valid sample is aggregated).
+    early_stop: float = 0.0
+    early_stop_slots: Tuple[int, ...] = (4, 8, 16)   # strictly increasing; boundaries >= SR are ignored
     is_train: int = 0
 
     @property
@@ -118,6 +124,13 @@ class HotPathOpts:
         w = self.depth_loss_weights
         return float(w[0] if len(w) == 1 else w[self.depth_loss_items.index("coarse_depth")])
 
+    @property
+    def early_stop_tiers(self):
+        """The slot ranges [lo, hi) a frame is aggregated in with early_stop > 0: [0, b0), [b0, b1), ...,
+        [b_last, SR) over the boundaries of early_stop_slots below SR."""
+        b = [0] + [int(x) for x in self.early_stop_slots if x < self.SR] + [int(self.SR)]
+        return tuple(zip(b[:-1], b[1:]))
+
     @classmethod
     def from_opt(cls, opt, **overrides):
         """Take every known field from a reference-style Namespace."""
@@ -131,6 +144,14 @@ class HotPathOpts:
                     if v is None:
                         continue
                     v = v if isinstance(v, tuple) else (v,)
+                if f.name == "early_stop_slots":   # unset (None), "4,8,16" or one bare value
+                    if v is None:
+                        continue
+                    if isinstance(v, str):
+                        v = tuple(int(x) for x in v.replace(",", " ").split())
+                    v = v if isinstance(v, tuple) else (int(v),)
+                if f.name == "early_stop" and v is None:
+                    continue
                 kw[f.name] = v
         kw.update(overrides)
         o = cls(**kw)
@@ -178,6 +199,13 @@ class HotPathOpts:
             bad.append(f"depth_loss_items: only coarse_depth is produced, not {', '.join(map(str, other))}")
         if self.depth_loss_items and len(self.depth_loss_weights) not in (1, len(self.depth_loss_items)):
             bad.append("depth_loss_weights must hold one weight or one per depth_loss_items entry")
+        es = self.early_stop
+        if isinstance(es, bool) or not isinstance(es, numbers.Real) or not 0.0 <= es < 1.0:   # NaN fails too
+            bad.append("early_stop (transmittance threshold) must satisfy 0 <= early_stop < 1")
+        sl = self.early_stop_slots
+        if (not isinstance(sl, tuple) or any(isinstance(x, bool) or not isinstance(x, numbers.Integral) or x <= 0 for x in sl)
+                or any(b <= a for a, b in zip(sl, sl[1:]))):
+            bad.append("early_stop_slots must be a tuple of strictly increasing positive slot boundaries")
         if bad:
             raise NotImplementedError("; ".join(bad))
         return self

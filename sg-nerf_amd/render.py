@@ -28,6 +28,10 @@ class RenderOut:
     blendw: torch.Tensor = None   # [R,SR] alpha-blend weight o*T (when want_weights)
     probe: torch.Tensor = None    # [R,48] packed hole-probing records (sgn_probe; when want_probe)
     depth: torch.Tensor = None    # [R] coarse_depth, 0 for invalid rays (sgn_composite_depth; when want_depth)
+    # early ray termination (opts.early_stop > 0 and the frame was aggregated tier by tier; else None)
+    stop_slot: torch.Tensor = None   # [R] int32: the slot boundary at which the ray was found finished, SR if never
+    skipped: torch.Tensor = None     # int32 scalar (device): valid samples that were not aggregated
+    tiers: torch.Tensor = None       # [n_tiers, 4] int32 (device): sgn_early_stop_tier's counters of each tier
 
 
 class PointTables:
@@ -97,6 +101,7 @@ class HipRenderer:
         self._fp = None        # sgn_frame_points buffers (marks, list, counts) for the projection subset
         self._pending = []   # deferred fp16-range checks: (pinned flag copy, event)
         self._flag_host = None
+        self._tiered = False   # the last frame was aggregated tier by tier (early ray termination)
 
     def set_mlp(self, mlp_state):
         self.mlp_state = {k: torch.as_tensor(v).detach().to("cpu", torch.float32)
@@ -131,13 +136,28 @@ class HipRenderer:
             self.probe = None
             self.depth = None
             self.viewdir = None   # [cap,3] rotated view direction per sample (rotated points only)
+            self.es = None        # early ray termination: (tier work list, tier counters, stop_slot, range flag)
             self._cap = (R, cap)
         if self.points.rot is not None and self.viewdir is None:
             self.viewdir = torch.zeros(self._cap[1], 3, dtype=torch.float32, device=self.device)
 
-    def _flag(self):
+    def _es_buffers(self):
+        """Early ray termination: the tier work list [cap], one counters row per tier, stop_slot [R] and the
+        fp16-range flag accumulated over a frame's tiers (f32 mode)."""
+        if self.es is None:
+            i32 = dict(dtype=torch.int32, device=self.device)
+            self.es = (torch.empty(self._cap[1], **i32), torch.zeros(len(self.opts.early_stop_tiers), 4, **i32),
+                       torch.empty(max(self._cap[0], 1), **i32), torch.zeros(1, **i32))
+        return self.es
+
+    def _ws_flag(self):
         off = int(_lib.lib().sgn_aggregate_flag_offset_f32(self.agg_ws.numel()))
         return self.agg_ws[off:off + 4].view(torch.int32)
+
+    def _flag(self):
+        """The fp16-range flag of the last frame: the workspace word of its colour stage, or, for a frame
+        aggregated tier by tier (every tier's colour stage clears that word), the OR over its tiers."""
+        return self.es[3] if self._tiered else self._ws_flag()
 
     def _range_check(self, mode, redo):
         """f32 mode: the colour stage flags samples whose decoded features are not finite (an
@@ -177,6 +197,16 @@ class HipRenderer:
                                 "check_range='deferred' are not finite; the renderer now uses the plain-fp32 path "
                                 "(sgn_aggregate_exact): render that frame again")
 
+    def _tiers(self, want_probe=False, want_weights=False, want_blend=False):
+        """The slot ranges of a frame aggregated tier by tier (opts.early_stop_tiers), or () for a frame
+        rendered in full: early_stop = 0, training options, per-slot outputs wanted (the aggregate
+        entries zero blend / wnorm on every call, and the hole probe must see every sample), or the
+        plain-fp32 range fallback."""
+        o = self.opts
+        if not o.early_stop > 0 or o.is_train or want_probe or want_weights or want_blend or self.exact:
+            return ()
+        return o.early_stop_tiers
+
     def finish(self):
         """Wait for the deferred range checks of the frames rendered so far (raises if one failed)."""
         while self._pending:
@@ -197,7 +227,19 @@ class HipRenderer:
         [R, 48]); implies want_opacity and want_blend.  `query_size`: overrides opts.query_size for this
         call (probe_hole's prob_kernel_size); the cached grid is kept.  `want_depth`: also the depth map
         (RenderOut.depth [R]: sum w z / (sum w + 1e-6) over the blend weights and the samples' camera-space z,
-        0 for rays without a valid sample; sgn_composite_depth in place of sgn_composite)."""
+        0 for rays without a valid sample; sgn_composite_depth in place of sgn_composite).
+
+        Early ray termination (opts.early_stop = eps > 0, no reference counterpart): the frame is aggregated
+        tier by tier over the slot ranges of opts.early_stop_tiers.  Before each tier sgn_early_stop_tier
+        recomputes every ray's transmittance T over the slots done so far; a ray with T <= eps is finished --
+        its remaining valid samples are not aggregated and get feat (0, 0, 0, 0), so the composite (run once
+        over the full query, unchanged) gives them opacity exactly 0.  A colour channel moves by at most
+        1.001 eps and bg_transmission rises by at most eps against the full render; ray_mask does not move.
+        RenderOut.stop_slot / skipped / tiers report what was skipped.  want_depth works (a skipped sample
+        has weight 0).  The option is ignored, and the frame rendered in full (those three fields None), with
+        want_probe, want_weights or want_blend (the aggregate entries zero the per-slot outputs on every call,
+        and the hole probe must see every sample), with opts.is_train, and on the plain-fp32 range fallback
+        (a frame whose tiers flag the fp16 range is re-rendered there in full)."""
         o = self.opts
         if want_probe:
             want_opacity = want_blend = True
@@ -269,28 +311,56 @@ class HipRenderer:
             project = L.sgn_point_project_f32 if self.f32 else L.sgn_point_project   # different arithmetic
             _lib.check(project(ctypes.byref(pt), _lib.ptr(self.packed), _lib.ptr(plist), _lib.ptr(pcount),
                                _lib.ptr(self._proj), st), "point projection (frame list)")
-        for stage, name in ((1, "agg_rows"), (2, "agg_color")):
-            mark(name)
-            blend = _lib.ptr(self.blend) if want_blend else None
-            wnorm = _lib.ptr(self.wnorm) if want_weights and stage == 1 else None
-            if self.exact:
-                if stage == 1:
-                    aggregate_exact()
-            elif self.f32:
-                _lib.check(L.sgn_aggregate_f32(nl, dim, bp, _lib.ptr(self._proj), ctypes.byref(pt), ctypes.byref(qo), cap, o.K,
-                                               _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
-                                               _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate_f32")
-            else:
-                _lib.check(L.sgn_aggregate(nl, dim, bp, _lib.ptr(self._proj), ctypes.byref(pt), ctypes.byref(qo), cap,
-                                           o.K, _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
-                                           _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate")
-        mark("composite")
         cp = _lib.CompositeParams()
         cp.SR, cp.vsize_z, cp.raydist_mode_unit = o.SR, float(o.vsize[2]), o.raydist_mode_unit
         if bg is None:
             bg = (1.0, 1.0, 1.0) if o.bg_color == "white" else (0.0, 0.0, 0.0)
         for i in range(3):
             cp.bg[i] = bg[i]
+
+        def aggregate(stage, qa):
+            blend = _lib.ptr(self.blend) if want_blend else None
+            wnorm = _lib.ptr(self.wnorm) if want_weights and stage == 1 else None
+            if self.f32:
+                _lib.check(L.sgn_aggregate_f32(nl, dim, bp, _lib.ptr(self._proj), ctypes.byref(pt), ctypes.byref(qa), cap, o.K,
+                                               _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
+                                               _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate_f32")
+            else:
+                _lib.check(L.sgn_aggregate(nl, dim, bp, _lib.ptr(self._proj), ctypes.byref(pt), ctypes.byref(qa), cap,
+                                           o.K, _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
+                                           _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate")
+
+        tiers = self._tiers(want_probe, want_weights, want_blend)
+        self._tiered = bool(tiers)
+        if tiers:
+            # early ray termination: tier by tier, every launch enqueued without a host sync.  Each tier's
+            # work list is built on the device from the transmittance over the slots already aggregated
+            # (sgn_early_stop_tier); the aggregators run on a copy of the query naming that list.
+            work, counters, stop_slot, flag = self._es_buffers()
+            stop_slot.fill_(o.SR)
+            flag.zero_()
+            qt = q.abi()
+            qt.work = work.data_ptr()
+            for t, (lo, hi) in enumerate(tiers):
+                mark("agg_tier" if t else "agg_rows")
+                qt.counters = counters[t].data_ptr()
+                _lib.check(L.sgn_early_stop_tier(ctypes.byref(cp), _lib.ptr(campos), _lib.ptr(rot), R, ctypes.byref(qo),
+                                                 _lib.ptr(self.feat), lo, hi, float(o.early_stop), cap, _lib.ptr(work),
+                                                 _lib.ptr(counters[t]), _lib.ptr(counters[t - 1]) if t else None,
+                                                 _lib.ptr(stop_slot), st), "sgn_early_stop_tier")
+                aggregate(1, qt)
+                aggregate(2, qt)
+                if self.f32:
+                    flag.bitwise_or_(self._ws_flag())
+        else:
+            for stage, name in ((1, "agg_rows"), (2, "agg_color")):
+                mark(name)
+                if self.exact:
+                    if stage == 1:
+                        aggregate_exact()
+                else:
+                    aggregate(stage, qo)
+        mark("composite")
 
         def composite():
             args = (ctypes.byref(cp), _lib.ptr(campos), _lib.ptr(rot), _lib.ptr(raydir), R, _lib.ptr(q.t_table),
@@ -315,9 +385,12 @@ class HipRenderer:
             probe()
         mark("end")
         self._range_check(check_range, lambda: (aggregate_exact(), composite(), probe()))
+        if self.exact:
+            tiers = ()   # the range fallback re-rendered the frame in full
         return RenderOut(self.rgb[:R], self.mask[:R], self.bgT[:R], self.opacity[:R], q, self.feat, self.blend,
                          self.wnorm if want_weights else None, self.blendw[:R] if want_weights else None,
-                         self.probe[:R] if want_probe else None, self.depth[:R] if want_depth else None)
+                         self.probe[:R] if want_probe else None, self.depth[:R] if want_depth else None,
+                         *((self.es[2][:R], self.es[1][-1, 2], self.es[1]) if tiers else ()))
 
     def points_projected(self):
         """The last frame's projected point count and the neighbour indices >= n_points met so far

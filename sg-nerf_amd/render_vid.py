@@ -78,6 +78,7 @@ def main(argv=None):
     ap.add_argument("--checkpoint", default=None, help="reference *_net_ray_marching.pth (weights_only load)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--precision", default="f32", choices=["f32", "f16"])
+    ap.add_argument("--early_stop", type=float, default=0.0, help="early ray termination threshold (0 = off)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -86,7 +87,7 @@ def main(argv=None):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group("nccl", device_id=dev)
-    o = HotPathOpts(SR=args.sr, precision=args.precision)
+    o = HotPathOpts(SR=args.sr, precision=args.precision, early_stop=args.early_stop)
     if args.checkpoint:
         from .ray_marching import NeuralPoints
         from .weights import strip_prefix
