@@ -759,8 +759,8 @@ typedef struct {
     float vsize_z;             /* vsize[2] */
     int32_t raydist_mode_unit;
     float bg[3];
-    float zero_one_weight;     /* 1e-4 (train_ft) */
-    float zero_one_eps;        /* 1e-3 */
+    float zero_one_weight;     /* zero_one_loss_weights[i] of conf_coefficient: 1e-4 (train_ft); 0: no gradient */
+    float zero_one_eps;        /* zero_epsilon: 1e-3 */
     const float *bg_ray;       /* device float[R*3], the rays' background (inputs['bg_ray'] of the
                                   plane background model, fill_invalid's T_bg * bg_ray,
                                   neural_points_volumetric_model.py:175-177); NULL: bg[3] for every ray */
@@ -801,6 +801,42 @@ int sgn_loss_train_depth(const sgn_loss_params *lp, const sgn_loss_depth *dp, co
                          const float *d_gt, const float *d_conf, float *d_out_rgb, int8_t *d_out_mask,
                          float *d_losses, float *d_dfeat, float *d_dconf, void *d_workspace, size_t workspace_bytes,
                          sgn_stream_t stream);
+
+/* The loss stage under the driver's loss options (ABI 23, an addition; opt.color_loss_items / color_loss_weights,
+ * zero_one_loss_items / zero_one_loss_weights, zero_epsilon, sparse_loss_weight of
+ * base_rendering_model.py:534-664; the zero-one weight and epsilon travel in sgn_loss_params).
+ *   total = w_masked d_losses[0] + w_miss d_losses[2] + w_all d_losses[3] + 1e-6 per listed colour item
+ *           + zero_one_weight d_losses[1] + sparse_weight d_losses[8] (+ dp->weight d_losses[7])
+ * and d_dfeat / d_dconf are d total / d feat, d conf.  A valid ray's d total / d rgb is
+ * (w_masked 2 / (3 n_valid) + w_all 2 / (3 R)) (c - gt), the scale made on the device once n_valid is known
+ * (no host read).  A missed ray's colour is its background, which carries no gradient: w_miss moves only the
+ * reported total and no kernel reads it.  zero_one_weight == 0 adds nothing to d_dconf; d_losses[1] is
+ * still reported.
+ * Sparse loss (sparse_weight > 0, :652-662): d_losses[8] = L = sum(wn |1 - exp(-2 cc)|) / (sum(wn) + 1e-6) over
+ * every (sample, neighbour) entry of the rays with out_mask 1, wn the aggregator's normalised neighbour weight
+ * (the linear distance kernel 1 / max(|xyz_p - x_s|, 1e-6) over the sample's neighbours, divided by
+ * max(their sum, 1e-8); 0 on empty entries; detached in the reference), restated by a small launch from q->pidx,
+ * xyz and q->samp_locw; cc the straight-through clamp of conf[p] to [1e-4, 1].  d_dconf[p] +=
+ * sparse_weight wn 2 exp(-2 cc) / (sum(wn) + 1e-6) (the clamp passes the gradient everywhere); nothing is added
+ * to d_dfeat.  d_losses[9] holds that scale, d_losses[10] sum(wn), d_losses[11] 0.
+ * d_losses is float[12] here.  dp NULL: no depth supervision (d_losses[7] = 0).  sparse_weight == 0 launches the
+ * kernels of sgn_loss_train / sgn_loss_train_depth (d_losses[8..11] = 0), and with (w_masked, w_miss, w_all) =
+ * (1, 0, 0) every output those entries write is theirs bit for bit.  The workspace is sized by
+ * sgn_loss_opts_workspace_bytes for every setting.  No host synchronisation; d_dconf NULL as sgn_loss_train
+ * (the sparse term is still reported). */
+typedef struct {
+    float w_masked, w_miss, w_all; /* weights of ray_masked_coarse_raycolor, ray_miss_coarse_raycolor,
+                                      coarse_raycolor (0 for an item that is not listed); >= 0 */
+    float sparse_weight;           /* sparse_loss_weight; >= 0 */
+    const float *xyz;              /* device float[N*3] point positions; required when sparse_weight > 0 */
+} sgn_loss_opts;
+
+size_t sgn_loss_opts_workspace_bytes(int64_t R, int32_t SR, int32_t K);
+int sgn_loss_train_opts(const sgn_loss_params *lp, const sgn_loss_opts *op, const sgn_loss_depth *dp,
+                        const float *d_campos, const float *d_camrotc2w, int64_t R, const sgn_query_out *q,
+                        const float *d_feat, const float *d_gt, const float *d_conf, float *d_out_rgb,
+                        int8_t *d_out_mask, float *d_losses, float *d_dfeat, float *d_dconf, void *d_workspace,
+                        size_t workspace_bytes, sgn_stream_t stream);
 
 /* ---- misc -------------------------------------------------------------- */
 int sgn_abi_version(void);

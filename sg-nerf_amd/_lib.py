@@ -74,6 +74,10 @@ class LossDepth(ctypes.Structure):
     _fields_ = [("gt_depth", c_vp), ("gt_mask", c_vp), ("weight", c_f32), ("out_depth", c_vp)]
 
 
+class LossOpts(ctypes.Structure):
+    _fields_ = [("w_masked", c_f32), ("w_miss", c_f32), ("w_all", c_f32), ("sparse_weight", c_f32), ("xyz", c_vp)]
+
+
 class GradSegment(ctypes.Structure):
     _fields_ = [("src", c_vp), ("tail", c_vp), ("dst", c_vp), ("n", c_i64), ("stride", c_i64), ("nb", c_i32),
                 ("reserved", c_i32)]
@@ -216,6 +220,10 @@ SIGNATURES = {
     "sgn_loss_train_depth": (c_i32, [ctypes.POINTER(LossParams), ctypes.POINTER(LossDepth), c_vp, c_vp, c_i64,
                                      ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                      c_sz, c_vp]),
+    "sgn_loss_opts_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32]),
+    "sgn_loss_train_opts": (c_i32, [ctypes.POINTER(LossParams), ctypes.POINTER(LossOpts), ctypes.POINTER(LossDepth),
+                                    c_vp, c_vp, c_i64, ctypes.POINTER(QueryOut), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp, c_vp, c_sz, c_vp]),
     "sgn_ray_march_dense": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, ctypes.POINTER(c_f32), c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_vp]),
 }

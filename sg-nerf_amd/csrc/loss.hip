@@ -24,6 +24,23 @@
 // loss vector's slot 7, and the reverse pass carries one more "colour channel" with the per-slot value
 // q_s = (z_s - D) / (W + 1e-6) and the weight d total / d D (no background term).  The DEPTH = false
 // instantiations are the stock kernels (they are passed a plain LossArgs).
+// The driver's loss options (sgn_loss_train_opts; opt.color_loss_items / color_loss_weights, zero_one_loss_weights,
+// zero_epsilon, sparse_loss_weight of base_rendering_model.py:534-664):
+//   colour weights  total holds w_masked L_masked + w_miss L_miss + w_all L_all.  A valid ray's d total / d rgb
+//                   is (w_masked 2 / (3 n_valid) + w_all 2 / (3 R)) (c - gt): one scale, made in k_loss_reduce where
+//                   n_valid becomes known.  A missed ray's colour is its background (no gradient), so w_miss moves
+//                   only the reported total: no kernel reads it.  (1, 0, 0) gives the stock scale's bits
+//                   (1 * x + 0 * y = x).
+//   sparse loss     SPARSE = true instantiations (sparse_loss_weight > 0, :652-662):
+//                   L = sum(wn |1 - exp(-2 cc)|) / (sum(wn) + 1e-6) over every (sample, k) entry of the valid rays,
+//                   wn the aggregator's normalised neighbour weight (detached there; 0 on empty entries), cc the
+//                   straight-through clamp of the gathered conf.  k_loss_nbw restates wn (the linear distance
+//                   kernel, point_aggregators.py:494-502, :946-947) from pidx, the points' xyz and samp_locw into
+//                   the workspace; the forward adds the two sums to the block partials, k_loss_reduce writes L to
+//                   slot 8 and sparse_w / (sum(wn) + 1e-6) to slot 9, the reverse pass adds
+//                   slot 9 * wn * 2 exp(-2 cc) into d conf with the zero-one term's atomic (the straight-through
+//                   clamp passes the gradient everywhere).  Nothing goes to d feat.  SPARSE = false are the
+//                   stock instantiations.
 #include <type_traits>
 
 #include "sgn_common.h"
@@ -43,6 +60,7 @@ struct LossArgs {
     int64_t R;
     int SR, K, unit;
     float vz, bg0, bg1, bg2, zo_w, zo_eps;
+    float w_masked, w_all;  // colour weights of ray_masked_coarse_raycolor / coarse_raycolor (stock: 1, 0)
     const float *bg_ray;  // [R][3] per-ray background (ABI 16, inputs['bg_ray']) or null: (bg0, bg1, bg2)
     float *slot_ws;   // [R][SR][3]: T (transmittance before the slot), e = exp(-sigma dist), dist
     float *partial;   // [blocks][LOSS_NSUM]
@@ -61,10 +79,17 @@ struct LossDepthArgs : LossArgs {
     float *out_depth;       // [R] D
     float *ray_w;           // [R] W (workspace), read by the reverse pass
 };
-template <bool DEPTH>
-using loss_args_t = std::conditional_t<DEPTH, LossDepthArgs, LossArgs>;
-template <bool DEPTH>
-constexpr int loss_nsum = DEPTH ? LOSS_NSUM + 1 : LOSS_NSUM;  // + the depth term's squared error
+// the sparse loss's arguments: the depth block (unused without DEPTH) first
+struct LossSparseArgs : LossDepthArgs {
+    const float *xyz;  // [N][3] point positions
+    float sparse_w;    // sparse_loss_weight
+    float *nbw;        // [R][SR][K] (workspace) normalised neighbour weight of the rays' (slot, k) entries
+};
+template <bool DEPTH, bool SPARSE>
+using loss_args_t = std::conditional_t<SPARSE, LossSparseArgs, std::conditional_t<DEPTH, LossDepthArgs, LossArgs>>;
+// + the depth term's squared error (index LOSS_NSUM), + the sparse loss's two sums (the last two)
+template <bool DEPTH, bool SPARSE>
+constexpr int loss_nsum = LOSS_NSUM + (DEPTH ? 1 : 0) + (SPARSE ? 2 : 0);
 
 __device__ __forceinline__ float depth_mask(const LossDepthArgs &a, int64_t r, float g) {
     return a.gt_mask ? a.gt_mask[r] : (g > 0.f ? 1.f : 0.f);
@@ -87,9 +112,13 @@ __device__ __forceinline__ float pers_z(const float *campos, const float *rot, f
 
 // zero-one term of one (slot, k) entry and its derivative w.r.t. the gathered conf (the straight-
 // through clamp passes the gradient unchanged, point_aggregators.py:863-865)
-__device__ __forceinline__ void zero_one(float cd, float eps, float &term, float &dterm) {
+__device__ __forceinline__ float clamped_conf(float cd) {
     const float cl = fminf(fmaxf(cd, 1e-4f), 1.f);
-    const float cc = __fsub_rn(cd, __fsub_rn(cd, cl));
+    return __fsub_rn(cd, __fsub_rn(cd, cl));
+}
+
+__device__ __forceinline__ void zero_one(float cd, float eps, float &term, float &dterm) {
+    const float cc = clamped_conf(cd);
     const float val = fminf(fmaxf(cc, eps), 1.f - eps);
     term = logf(val) + logf(1.f - val);
     dterm = (cc >= eps && cc <= 1.f - eps) ? 1.f / val - 1.f / (1.f - val) : 0.f;
@@ -168,9 +197,38 @@ __device__ __forceinline__ float block_sum(float v, float *red) {
     return t;
 }
 
-template <bool DEPTH>
-__global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(loss_args_t<DEPTH> a) {
-    constexpr int NSUM = loss_nsum<DEPTH>;
+// The aggregator's normalised neighbour weights of slot s of ray r, one thread per (ray, slot):
+// 1 / max(|xyz_p - x_s|, 1e-6) over the slot's neighbours (0 on empty entries), divided by max(their sum, 1e-8),
+// k ascending (point_aggregators.py:494-502 linear, :946-947; train.aggregate).  Slots past the ray's samples
+// are neither written here nor read later.
+__global__ __launch_bounds__(LOSS_TPB) void k_loss_nbw(LossSparseArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * LOSS_TPB + threadIdx.x;
+    if (i >= a.R * a.SR) return;
+    const int64_t r = i / a.SR;
+    const int s = (int)(i - r * a.SR);
+    if (s >= a.ray_ns[r]) return;
+    const int64_t id = (int64_t)a.ray_soff[r] + s;
+    const float x = a.samp_locw[id * 3], y = a.samp_locw[id * 3 + 1], z = a.samp_locw[id * 3 + 2];
+    float *w = a.nbw + i * a.K;
+    float sum = 0.f;
+    for (int k = 0; k < a.K; ++k) {
+        const int p = a.pidx[id * a.K + k];
+        float v = 0.f;
+        if (p >= 0) {
+            const float dx = a.xyz[(int64_t)p * 3] - x, dy = a.xyz[(int64_t)p * 3 + 1] - y,
+                        dz = a.xyz[(int64_t)p * 3 + 2] - z;
+            v = 1.f / fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-6f);
+        }
+        w[k] = v;
+        sum += v;
+    }
+    const float den = fmaxf(sum, 1e-8f);
+    for (int k = 0; k < a.K; ++k) w[k] = w[k] / den;
+}
+
+template <bool DEPTH, bool SPARSE>
+__global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(loss_args_t<DEPTH, SPARSE> a) {
+    constexpr int NSUM = loss_nsum<DEPTH, SPARSE>;
     __shared__ float red[LOSS_TPB / 64];
     const int64_t r = ((int64_t)blockIdx.x * LOSS_TPB + threadIdx.x) / LPR;
     const int sub = threadIdx.x % LPR;
@@ -200,7 +258,7 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(loss_args_t<DEPTH> a) {
                 a.ray_w[r] = dW;
                 const float g = a.gt_depth[r];
                 const float md = depth_mask(a, r, g) * (D - g);
-                v[NSUM - 1] = md * md;
+                v[LOSS_NSUM] = md * md;
             }
         }
         if (any) {  // zero-one terms over the ray's SR x K entries, neighbour k = sub, sub + 8, ..
@@ -209,6 +267,7 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(loss_args_t<DEPTH> a) {
             float t0, d0;
             zero_one(a.conf[0], a.zo_eps, t0, d0);
             float zs = 0.f;
+            float sl = 0.f, sw = 0.f;  // SPARSE: sum wn |1 - exp(-2 cc)|, sum wn (empty entries weigh 0)
             int n_empty = 0;
             for (int k = sub; k < a.K; k += LPR) {
                 n_empty += a.SR - nv;
@@ -221,9 +280,18 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(loss_args_t<DEPTH> a) {
                     float t, d;
                     zero_one(a.conf[p], a.zo_eps, t, d);
                     zs += t;
+                    if constexpr (SPARSE) {
+                        const float wn = a.nbw[(r * a.SR + s2) * a.K + k];
+                        sl += wn * fabsf(1.f - expf(-2.f * clamped_conf(a.conf[p])));
+                        sw += wn;
+                    }
                 }
             }
             v[3] = zs + (float)n_empty * t0;
+            if constexpr (SPARSE) {
+                v[NSUM - 2] = sl;
+                v[NSUM - 1] = sw;
+            }
         }
     }
     for (int i = 0; i < NSUM; ++i) {
@@ -232,9 +300,9 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_fwd(loss_args_t<DEPTH> a) {
     }
 }
 
-template <bool DEPTH>
-__global__ __launch_bounds__(LOSS_TPB) void k_loss_reduce(loss_args_t<DEPTH> a, int nblocks) {
-    constexpr int NSUM = loss_nsum<DEPTH>;
+template <bool DEPTH, bool SPARSE>
+__global__ __launch_bounds__(LOSS_TPB) void k_loss_reduce(loss_args_t<DEPTH, SPARSE> a, int nblocks) {
+    constexpr int NSUM = loss_nsum<DEPTH, SPARSE>;
     __shared__ float red[LOSS_TPB / 64];
     float t[NSUM];
     for (int i = 0; i < NSUM; ++i) {
@@ -249,20 +317,27 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_reduce(loss_args_t<DEPTH> a, 
         a.sums[1] = t[3] / den_z;
         a.sums[2] = t[1] / 3.f;
         a.sums[3] = t[2] / (3.f * (float)a.R);
-        a.sums[4] = 2.f / den_c;
+        // d total / d rgb of a valid ray over (c - gt); w_masked = 1, w_all = 0: 2 / den_c, bit for bit
+        a.sums[4] = a.w_masked * (2.f / den_c) + a.w_all * (2.f / (3.f * (float)a.R));
         a.sums[5] = a.zo_w / den_z;
         a.sums[6] = n;
         if constexpr (DEPTH)
-            a.sums[7] = t[NSUM - 1] / (float)a.R;  // L_depth: MSELoss over all R rays
+            a.sums[7] = t[LOSS_NSUM] / (float)a.R;  // L_depth: MSELoss over all R rays
         else
             a.sums[7] = 0.f;
+        if constexpr (SPARSE) {  // the loss vector of sgn_loss_train_opts has 12 slots
+            const float den_s = t[NSUM - 1] + 1e-6f;
+            a.sums[8] = t[NSUM - 2] / den_s;
+            a.sums[9] = a.sparse_w / den_s;
+            a.sums[10] = t[NSUM - 1];
+        }
     }
 }
 
 // CONF: points_conf is trained (dconf non-NULL); frozen, the zero-one term is still in the loss
 // (k_loss_fwd) and only its gradient -- the loop below, point 0's empty-slot term included -- goes
-template <bool CONF, bool DEPTH>
-__global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(loss_args_t<DEPTH> a) {
+template <bool CONF, bool DEPTH, bool SPARSE>
+__global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(loss_args_t<DEPTH, SPARSE> a) {
     const int64_t r = ((int64_t)blockIdx.x * LOSS_TPB + threadIdx.x) / LPR;
     const int sub = threadIdx.x % LPR;
     if (r >= a.R) return;
@@ -320,7 +395,13 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(loss_args_t<DEPTH> a) {
     }
     if constexpr (!CONF) return;
     // zero-one gradients, neighbour k = sub, sub + 8, ..; the empty entries all read conf[0]
+    // SPARSE: each entry's sparse gradient rides the same add (its weight is 0 on the empty entries)
     const float gz = a.sums[5];
+    if constexpr (!SPARSE) {
+        if (gz == 0.f) return;  // zero-one weight 0: nothing to add
+    }
+    float gsp = 0.f;
+    if constexpr (SPARSE) gsp = a.sums[9];
     float t0, d0;
     zero_one(a.conf[0], a.zo_eps, t0, d0);
     int n_empty = 0;
@@ -334,14 +415,35 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(loss_args_t<DEPTH> a) {
             }
             float t, d;
             zero_one(a.conf[p], a.zo_eps, t, d);
-            if (d != 0.f) atomicAdd(a.dconf + p, gz * d);
+            if constexpr (SPARSE) {
+                const float wn = a.nbw[(r * SR + s) * a.K + k];
+                const float g = gz * d + gsp * wn * (2.f * expf(-2.f * clamped_conf(a.conf[p])));
+                if (g != 0.f) atomicAdd(a.dconf + p, g);
+            } else {
+                if (d != 0.f) atomicAdd(a.dconf + p, gz * d);
+            }
         }
     }
-    if (n_empty > 0 && d0 != 0.f) atomicAdd(a.dconf, gz * d0 * (float)n_empty);
+    if (n_empty > 0 && d0 != 0.f && gz != 0.f) atomicAdd(a.dconf, gz * d0 * (float)n_empty);
 }
 
 }  // namespace
 }  // namespace sgn
+
+// the three launches (after k_loss_nbw with SPARSE) of one instantiation; `a` is cut down to its argument block
+template <bool DEPTH, bool SPARSE>
+static void loss_kernels(const sgn::LossSparseArgs &a, int64_t nb, bool conf, hipStream_t st) {
+    using namespace sgn;
+    const dim3 grid((unsigned)nb), one(1), tpb(LOSS_TPB);
+    const loss_args_t<DEPTH, SPARSE> &b = a;
+    if constexpr (SPARSE) {
+        const dim3 gw((unsigned)((a.R * a.SR + LOSS_TPB - 1) / LOSS_TPB));
+        hipLaunchKernelGGL(k_loss_nbw, gw, tpb, 0, st, a);
+    }
+    hipLaunchKernelGGL((k_loss_fwd<DEPTH, SPARSE>), grid, tpb, 0, st, b);
+    hipLaunchKernelGGL((k_loss_reduce<DEPTH, SPARSE>), one, tpb, 0, st, b, (int)nb);
+    hipLaunchKernelGGL((conf ? k_loss_bwd<true, DEPTH, SPARSE> : k_loss_bwd<false, DEPTH, SPARSE>), grid, tpb, 0, st, b);
+}
 
 extern "C" {
 
@@ -351,11 +453,11 @@ size_t sgn_loss_workspace_bytes(int64_t R, int32_t SR) {
     return (size_t)(R * SR * 3 * 4 + (nb + 1) * sgn::LOSS_NSUM * 4 + 64);
 }
 
-static int loss_launch(const sgn_loss_params *lp, const sgn_loss_depth *dp, const float *d_campos,
-                       const float *d_camrotc2w, int64_t R, const sgn_query_out *q, const float *d_feat,
-                       const float *d_gt, const float *d_conf, float *d_out_rgb, int8_t *d_out_mask, float *d_losses,
-                       float *d_dfeat, float *d_dconf, void *d_workspace, size_t workspace_bytes, bool depth,
-                       sgn_stream_t stream) {
+static int loss_launch(const sgn_loss_params *lp, const sgn_loss_opts *op, const sgn_loss_depth *dp,
+                       const float *d_campos, const float *d_camrotc2w, int64_t R, const sgn_query_out *q,
+                       const float *d_feat, const float *d_gt, const float *d_conf, float *d_out_rgb,
+                       int8_t *d_out_mask, float *d_losses, float *d_dfeat, float *d_dconf, void *d_workspace,
+                       size_t workspace_bytes, bool depth, sgn_stream_t stream) {
     using namespace sgn;
     SGN_REQUIRE(lp && q && d_campos && d_camrotc2w && d_feat && d_gt && d_conf && d_out_rgb && d_out_mask &&
                     d_losses && d_dfeat && d_workspace,
@@ -363,13 +465,21 @@ static int loss_launch(const sgn_loss_params *lp, const sgn_loss_depth *dp, cons
     SGN_REQUIRE(!depth || (dp && dp->gt_depth && dp->out_depth), "null argument");
     SGN_REQUIRE(lp->SR > 0 && lp->K > 0, "SR and K must be positive");
     SGN_REQUIRE(R >= 0, "R must be non-negative");
-    SGN_REQUIRE(workspace_bytes >= (depth ? sgn_loss_depth_workspace_bytes(R, lp->SR) : sgn_loss_workspace_bytes(R, lp->SR)),
+    const bool sparse = op && op->sparse_weight > 0.f;
+    if (op) {
+        SGN_REQUIRE(op->w_masked >= 0.f && op->w_miss >= 0.f && op->w_all >= 0.f && op->sparse_weight >= 0.f,
+                    "loss weights must be non-negative");
+        SGN_REQUIRE(!sparse || op->xyz, "the sparse loss needs the points' xyz");
+    }
+    SGN_REQUIRE(workspace_bytes >= (op      ? sgn_loss_opts_workspace_bytes(R, lp->SR, lp->K)
+                                    : depth ? sgn_loss_depth_workspace_bytes(R, lp->SR)
+                                            : sgn_loss_workspace_bytes(R, lp->SR)),
                 "loss workspace too small");
     SGN_REQUIRE(((uintptr_t)d_feat & 15) == 0 && ((uintptr_t)d_dfeat & 15) == 0 && ((uintptr_t)d_workspace & 15) == 0,
                 "16-byte alignment required");
     hipStream_t st = as_stream(stream);
     const int64_t nb = (R * LPR + LOSS_TPB - 1) / LOSS_TPB;
-    LossDepthArgs a{};
+    LossSparseArgs a{};
     a.campos = d_campos; a.rot = d_camrotc2w;
     a.ray_ns = q->ray_ns; a.ray_soff = q->ray_soff; a.samp_nnb = q->samp_nnb; a.pidx = q->pidx;
     a.samp_locw = q->samp_locw; a.feat = d_feat; a.gt = d_gt; a.conf = d_conf;
@@ -377,29 +487,33 @@ static int loss_launch(const sgn_loss_params *lp, const sgn_loss_depth *dp, cons
     a.bg0 = lp->bg[0]; a.bg1 = lp->bg[1]; a.bg2 = lp->bg[2];
     a.bg_ray = lp->bg_ray;
     a.zo_w = lp->zero_one_weight; a.zo_eps = lp->zero_one_eps;
+    a.w_masked = op ? op->w_masked : 1.f; a.w_all = op ? op->w_all : 0.f;
     a.slot_ws = (float *)d_workspace;
     a.partial = a.slot_ws + R * lp->SR * 3;
     a.sums = d_losses;
     a.out_rgb = d_out_rgb; a.out_mask = d_out_mask; a.dfeat = d_dfeat; a.dconf = d_dconf;
+    if (sparse) {  // workspace: slots, the entries' weights, (W per ray,) partials
+        a.xyz = op->xyz; a.sparse_w = op->sparse_weight;
+        a.nbw = a.partial;
+        a.partial = a.nbw + R * lp->SR * lp->K;
+    }
     if (depth) {  // workspace: slots, W per ray, partials
         a.gt_depth = dp->gt_depth; a.gt_mask = dp->gt_mask; a.depth_w = dp->weight; a.out_depth = dp->out_depth;
         a.ray_w = a.partial;
         a.partial = a.ray_w + R;
     }
+    if (op)  // the loss vector's slots 8..11: L_sparse, its gradient scale, sum(wn), spare (0 without the sparse loss)
+        SGN_CHECK_HIP(hipMemsetAsync(d_losses + 8, 0, 4 * sizeof(float), st));
     if (R == 0) {
         SGN_CHECK_HIP(hipMemsetAsync(d_losses, 0, 8 * sizeof(float), st));
         return 0;
     }
-    const dim3 grid((unsigned)nb), one(1), tpb(LOSS_TPB);
-    if (depth) {
-        hipLaunchKernelGGL(k_loss_fwd<true>, grid, tpb, 0, st, a);
-        hipLaunchKernelGGL(k_loss_reduce<true>, one, tpb, 0, st, a, (int)nb);
-        hipLaunchKernelGGL((d_dconf ? k_loss_bwd<true, true> : k_loss_bwd<false, true>), grid, tpb, 0, st, a);
+    if (sparse) {
+        if (depth) loss_kernels<true, true>(a, nb, d_dconf != nullptr, st);
+        else loss_kernels<false, true>(a, nb, d_dconf != nullptr, st);
     } else {
-        const LossArgs &b = a;
-        hipLaunchKernelGGL(k_loss_fwd<false>, grid, tpb, 0, st, b);
-        hipLaunchKernelGGL(k_loss_reduce<false>, one, tpb, 0, st, b, (int)nb);
-        hipLaunchKernelGGL((d_dconf ? k_loss_bwd<true, false> : k_loss_bwd<false, false>), grid, tpb, 0, st, b);
+        if (depth) loss_kernels<true, false>(a, nb, d_dconf != nullptr, st);
+        else loss_kernels<false, false>(a, nb, d_dconf != nullptr, st);
     }
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
@@ -415,8 +529,8 @@ int sgn_loss_train(const sgn_loss_params *lp, const float *d_campos, const float
                    const sgn_query_out *q, const float *d_feat, const float *d_gt, const float *d_conf,
                    float *d_out_rgb, int8_t *d_out_mask, float *d_losses, float *d_dfeat, float *d_dconf,
                    void *d_workspace, size_t workspace_bytes, sgn_stream_t stream) {
-    return loss_launch(lp, nullptr, d_campos, d_camrotc2w, R, q, d_feat, d_gt, d_conf, d_out_rgb, d_out_mask, d_losses,
-                       d_dfeat, d_dconf, d_workspace, workspace_bytes, false, stream);
+    return loss_launch(lp, nullptr, nullptr, d_campos, d_camrotc2w, R, q, d_feat, d_gt, d_conf, d_out_rgb, d_out_mask,
+                       d_losses, d_dfeat, d_dconf, d_workspace, workspace_bytes, false, stream);
 }
 
 int sgn_loss_train_depth(const sgn_loss_params *lp, const sgn_loss_depth *dp, const float *d_campos,
@@ -424,8 +538,24 @@ int sgn_loss_train_depth(const sgn_loss_params *lp, const sgn_loss_depth *dp, co
                          const float *d_gt, const float *d_conf, float *d_out_rgb, int8_t *d_out_mask,
                          float *d_losses, float *d_dfeat, float *d_dconf, void *d_workspace, size_t workspace_bytes,
                          sgn_stream_t stream) {
-    return loss_launch(lp, dp, d_campos, d_camrotc2w, R, q, d_feat, d_gt, d_conf, d_out_rgb, d_out_mask, d_losses,
-                       d_dfeat, d_dconf, d_workspace, workspace_bytes, true, stream);
+    return loss_launch(lp, nullptr, dp, d_campos, d_camrotc2w, R, q, d_feat, d_gt, d_conf, d_out_rgb, d_out_mask,
+                       d_losses, d_dfeat, d_dconf, d_workspace, workspace_bytes, true, stream);
+}
+
+size_t sgn_loss_opts_workspace_bytes(int64_t R, int32_t SR, int32_t K) {
+    if (R < 0 || SR <= 0 || K <= 0) return 0;
+    const int64_t nb = (R * sgn::LPR + sgn::LOSS_TPB - 1) / sgn::LOSS_TPB;
+    return (size_t)(R * SR * 3 * 4 + R * SR * K * 4 + R * 4 + (nb + 1) * (sgn::LOSS_NSUM + 3) * 4 + 64);
+}
+
+int sgn_loss_train_opts(const sgn_loss_params *lp, const sgn_loss_opts *op, const sgn_loss_depth *dp,
+                        const float *d_campos, const float *d_camrotc2w, int64_t R, const sgn_query_out *q,
+                        const float *d_feat, const float *d_gt, const float *d_conf, float *d_out_rgb,
+                        int8_t *d_out_mask, float *d_losses, float *d_dfeat, float *d_dconf, void *d_workspace,
+                        size_t workspace_bytes, sgn_stream_t stream) {
+    SGN_REQUIRE(op, "null argument");
+    return loss_launch(lp, op, dp, d_campos, d_camrotc2w, R, q, d_feat, d_gt, d_conf, d_out_rgb, d_out_mask, d_losses,
+                       d_dfeat, d_dconf, d_workspace, workspace_bytes, dp != nullptr, stream);
 }
 
 }  // extern "C"

@@ -235,7 +235,9 @@ class HipPointsVolumetricModel:
         self.optimizers = [self.trainer.opt_net, self.trainer.opt_pts]
         self.schedulers = []
         # the depth loss is listed while depth supervision is on (base_rendering_model.py:611-618)
-        self.loss_names = list(LOSS_NAMES) + (["coarse_depth"] if self.opts.depth_loss_weight is not None else [])
+        # and the sparse loss while sparse_loss_weight > 0 (:652-662)
+        self.loss_names = (list(LOSS_NAMES) + (["coarse_depth"] if self.opts.depth_loss_weight is not None else [])
+                           + (["sparse"] if self.opts.sparse_loss_weight > 0 else []))
 
     def init_scheduler(self, total_steps, opt):
         """iter_exponential_decay resumed at total_steps (the reference steps its schedulers that often)."""

@@ -7,9 +7,12 @@ models/neural_points_volumetric_model.py:63-124).  Defaults below are the
 ScanNet values of dev_scripts/w_scannet_etf/scene241.sh:11-106 and
 pointnerf/run/checkpoints/scannet/scene0710_00640480/opt.txt.
 """
+import math
 import numbers
 from dataclasses import dataclass, field, fields, replace
 from typing import Tuple
+
+COLOR_LOSS_ITEMS = ("ray_masked_coarse_raycolor", "ray_miss_coarse_raycolor", "coarse_raycolor")
 
 
 @dataclass(frozen=True)
@@ -84,6 +87,18 @@ class HotPathOpts:
     compute_depth: int = 0
     depth_loss_items: Tuple[str, ...] = ()
     depth_loss_weights: Tuple[float, ...] = (1.0,)
+    # the training objective (base_rendering_model.py:534-664).  Colour items in any order or a subset, one weight
+    # per item (or one for all), each listed item adding weight * loss + 1e-6; the zero-one loss on
+    # conf_coefficient (an empty item list drops it); sparse_loss_weight > 0 adds the sparse loss on conf
+    # (:652-662, reported as "sparse").  The defaults are the ScanNet opt.txt.  bg / l2_size items are refused.
+    color_loss_items: Tuple[str, ...] = COLOR_LOSS_ITEMS
+    color_loss_weights: Tuple[float, ...] = (1.0, 0.0, 0.0)
+    zero_one_loss_items: Tuple[str, ...] = ("conf_coefficient",)
+    zero_one_loss_weights: Tuple[float, ...] = (1e-4,)
+    zero_epsilon: float = 1e-3
+    sparse_loss_weight: float = 0.0
+    bg_loss_items: Tuple[str, ...] = ()
+    l2_size_loss_items: Tuple[str, ...] = ()
     # knobs of this implementation (no reference counterpart)
     # aggregator arithmetic: "f32" = the reference's fp32 products, each carried as three fp16 MFMA
     # products with fp32 accumulation (mlp_x3.hip); "f16" = fp16 MFMA operands (mlp.hip, faster)
@@ -124,6 +139,50 @@ class HotPathOpts:
         w = self.depth_loss_weights
         return float(w[0] if len(w) == 1 else w[self.depth_loss_items.index("coarse_depth")])
 
+    @staticmethod
+    def _item_weight(items, weights, name):
+        """weights[i] of `name` in items (one weight serves every item), 0.0 when it is not listed."""
+        if name not in items:
+            return 0.0
+        return float(weights[0] if len(weights) == 1 else weights[items.index(name)])
+
+    @property
+    def color_weights(self):
+        """(w_masked, w_miss, w_all): the weights of the three colour items, 0 for one that is not listed."""
+        return tuple(self._item_weight(self.color_loss_items, self.color_loss_weights, n) for n in COLOR_LOSS_ITEMS)
+
+    @property
+    def zero_one_weight(self):
+        """The weight of the zero-one loss on conf_coefficient, 0 when it is not listed."""
+        return self._item_weight(self.zero_one_loss_items, self.zero_one_loss_weights, "conf_coefficient")
+
+    @property
+    def stock_loss(self):
+        """Whether the loss stage runs its stock entries: the ScanNet colour weights and no sparse loss (the
+        zero-one weight and epsilon travel in the stock parameters)."""
+        return self.color_weights == (1.0, 0.0, 0.0) and not self.sparse_loss_weight > 0
+
+    def total_loss(self, parts, depth_weight=None, zero_one_weight=None):
+        """loss_total from the reported parts (a mapping of the items' names, "conf_coefficient", "sparse" and
+        "coarse_depth" to scalars), as compute_losses adds it up: weight * loss + 1e-6 per listed colour item,
+        then the zero-one, sparse and depth terms.  Items of weight 0 only leave their 1e-6 (the defaults give
+        ray_masked + 3e-6 + 1e-4 * conf_coefficient, in this order).  zero_one_weight: a caller's override."""
+        zw = self.zero_one_weight if zero_one_weight is None else zero_one_weight
+        total = None
+        for name, w in zip(COLOR_LOSS_ITEMS, self.color_weights):
+            if w != 0.0:
+                t = parts[name] if w == 1.0 else w * parts[name]
+                total = t if total is None else total + t
+        eps = len(self.color_loss_items) / 1e6
+        total = eps if total is None else total + eps
+        if zw != 0.0:
+            total = total + zw * parts["conf_coefficient"]
+        if self.sparse_loss_weight > 0:
+            total = total + self.sparse_loss_weight * parts["sparse"]
+        if depth_weight is not None:
+            total = total + depth_weight * parts["coarse_depth"]
+        return total
+
     @property
     def early_stop_tiers(self):
         """The slot ranges [lo, hi) a frame is aggregated in with early_stop > 0: [0, b0), [b0, b1), ...,
@@ -140,7 +199,9 @@ class HotPathOpts:
                 v = getattr(opt, f.name)
                 if isinstance(v, list):
                     v = tuple(v)
-                if f.name in ("depth_loss_items", "depth_loss_weights"):   # unset (None) or one bare value
+                if f.name in ("depth_loss_items", "depth_loss_weights", "color_loss_items", "color_loss_weights",
+                              "zero_one_loss_items", "zero_one_loss_weights", "bg_loss_items",
+                              "l2_size_loss_items"):   # unset (None) or one bare value
                     if v is None:
                         continue
                     v = v if isinstance(v, tuple) else (v,)
@@ -150,9 +211,14 @@ class HotPathOpts:
                     if isinstance(v, str):
                         v = tuple(int(x) for x in v.replace(",", " ").split())
                     v = v if isinstance(v, tuple) else (int(v),)
-                if f.name == "early_stop" and v is None:
+                if f.name in ("early_stop", "zero_epsilon", "sparse_loss_weight") and v is None:
                     continue
                 kw[f.name] = v
+        # argparse's lone default weight beside unset items (color_loss_items None, color_loss_weights [1.0]):
+        # the ScanNet items keep their ScanNet weights
+        for items, weights in (("color_loss_items", "color_loss_weights"), ("zero_one_loss_items", "zero_one_loss_weights")):
+            if items not in kw and len(kw.get(weights, ())) == 1:
+                del kw[weights]
         kw.update(overrides)
         o = cls(**kw)
         if o.query_size[0] == 0:  # neural_points.py:425
@@ -199,6 +265,36 @@ class HotPathOpts:
             bad.append(f"depth_loss_items: only coarse_depth is produced, not {', '.join(map(str, other))}")
         if self.depth_loss_items and len(self.depth_loss_weights) not in (1, len(self.depth_loss_items)):
             bad.append("depth_loss_weights must hold one weight or one per depth_loss_items entry")
+        def weights_ok(w):
+            return all(not isinstance(x, bool) and isinstance(x, numbers.Real) and math.isfinite(x) and x >= 0 for x in w)
+        other = [i for i in self.color_loss_items if i not in COLOR_LOSS_ITEMS]
+        if other:
+            bad.append(f"color_loss_items: only {', '.join(COLOR_LOSS_ITEMS)} are produced, not "
+                       f"{', '.join(map(str, other))}")
+        if len(set(self.color_loss_items)) != len(self.color_loss_items):
+            bad.append("color_loss_items must not repeat an item")
+        if self.color_loss_items and len(self.color_loss_weights) not in (1, len(self.color_loss_items)):
+            bad.append("color_loss_weights must hold one weight or one per color_loss_items entry")
+        if not weights_ok(self.color_loss_weights):
+            bad.append("color_loss_weights must be finite and non-negative")
+        other = [i for i in self.zero_one_loss_items if i != "conf_coefficient"]
+        if other:
+            bad.append(f"zero_one_loss_items: only conf_coefficient is produced, not {', '.join(map(str, other))}")
+        if len(self.zero_one_loss_items) > 1:
+            bad.append("zero_one_loss_items must not repeat an item")
+        if self.zero_one_loss_items and len(self.zero_one_loss_weights) not in (1, len(self.zero_one_loss_items)):
+            bad.append("zero_one_loss_weights must hold one weight or one per zero_one_loss_items entry")
+        if not weights_ok(self.zero_one_loss_weights):
+            bad.append("zero_one_loss_weights must be finite and non-negative")
+        ze = self.zero_epsilon
+        if isinstance(ze, bool) or not isinstance(ze, numbers.Real) or not 0.0 < ze < 0.5:   # NaN fails too
+            bad.append("zero_epsilon must satisfy 0 < zero_epsilon < 0.5")
+        if not weights_ok((self.sparse_loss_weight,)):
+            bad.append("sparse_loss_weight must be finite and non-negative")
+        if self.bg_loss_items:
+            bad.append("bg_loss_items must be empty (the background loss is not implemented)")
+        if self.l2_size_loss_items:
+            bad.append("l2_size_loss_items must be empty (the l2 size loss is not implemented)")
         es = self.early_stop
         if isinstance(es, bool) or not isinstance(es, numbers.Real) or not 0.0 <= es < 1.0:   # NaN fails too
             bad.append("early_stop (transmittance threshold) must satisfy 0 <= early_stop < 1")

@@ -214,7 +214,7 @@ def depth_target(gt_depth, gt_mask, weight, R, device):
 
 
 def loss_from_query(points, mlp, q, campos, rot, raydir, gt, opts: HotPathOpts, bg=(1.0, 1.0, 1.0),
-                    zero_one_weight=1e-4, zero_eps=1e-3, depth=None):
+                    zero_one_weight=None, zero_eps=None, depth=None):
     """Reference losses for one batch given a sample-major query result q (dict of tensors:
     ray_ns [R], ray_soff [R], samp_ray [S], samp_locw [S,3], pidx [S,K]).
     Returns (total loss, dict of parts, rendered colour [R,3], ray_mask [R]) and, with `depth` (a
@@ -244,8 +244,18 @@ class _CumprodPositive(torch.autograd.Function):
         return (grad * out).flip(-1).cumsum(-1).flip(-1).div(x)
 
 
+def neighbour_weights(xyz, samp_locw, pidx):
+    """The aggregator's normalised neighbour weights [S, K] (the linear distance kernel, point_aggregators.py:
+    494-502, :946-947, as `aggregate` computes them), detached; 0 on empty entries."""
+    with torch.no_grad():
+        mask = pidx >= 0
+        d = xyz[torch.clamp(pidx, 0, xyz.shape[0] - 1).reshape(-1).long()].view(*pidx.shape, 3) - samp_locw[:, None, :]
+        w = mask / torch.clamp(torch.norm(d, dim=-1), min=1e-6)
+        return w / torch.clamp(torch.sum(w, dim=-1, keepdim=True), min=1e-8)
+
+
 def composite_losses(points, q, feat, valid, campos, rot, raydir, gt, opts: HotPathOpts, bg=(1.0, 1.0, 1.0),
-                     zero_one_weight=1e-4, zero_eps=1e-3, s_count=None, depth=None):
+                     zero_one_weight=None, zero_eps=None, s_count=None, depth=None):
     """ray_dist + ray_march + the reference losses from per-sample features feat [S,4]
     (alpha, r, g, b) and the per-sample validity (>= 1 neighbour).  bg: a constant colour (3
     floats) or the rays' background [R, 3] (the plane model's bg_ray: T_bg * bg_ray + colour).
@@ -254,12 +264,20 @@ def composite_losses(points, q, feat, valid, campos, rot, raydir, gt, opts: HotP
     real; the rest (capacity padding, for a graph-captured step with static shapes) are routed
     to a sentinel ray row that is dropped, so the result equals the unpadded call.
 
+    The objective is the options' (base_rendering_model.py:534-664): each listed colour item adds
+    weight * loss + 1e-6 (opts.color_loss_items / color_loss_weights), the zero-one loss on conf_coefficient
+    takes opts.zero_one_weight and opts.zero_epsilon (zero_one_weight / zero_eps override them), and
+    opts.sparse_loss_weight > 0 adds sum(wn |1 - exp(-2 cc)|) / (sum(wn) + 1e-6) over the valid rays' entries
+    (:652-662; wn = neighbour_weights, cc the clamped conf), reported as parts['sparse'].
+
     depth (a DepthTarget): depth supervision.  D = sum_s w_s z_s / (sum_s w_s + 1e-6) over the blend weights
     w = o T and the samples' raw camera-space z (coarse_depth, neural_points_volumetric_model.py:620-624), 0 on
     rays outside ray_mask; L = mean over all R rays of (m (D - gt))^2 is added with depth.weight and reported
     as parts['coarse_depth']; the depth map [R] is returned as a fifth value."""
     R = raydir.shape[0]
     SR = opts.SR
+    zero_one_weight = opts.zero_one_weight if zero_one_weight is None else zero_one_weight
+    zero_eps = opts.zero_epsilon if zero_eps is None else zero_eps
     campos = campos.reshape(1, 3)
     rot = rot.reshape(3, 3)
     S = q["samp_ray"].shape[0]
@@ -307,8 +325,12 @@ def composite_losses(points, q, feat, valid, campos, rot, raydir, gt, opts: HotP
     # ray_miss_coarse_raycolor (:553-563) = mse over the missed rays x their count = their sum / 3;
     # coarse_raycolor = mse over every ray.  Both carry weight 0: logged, and ranked per frame by
     # the probe (mvs_points_volumetric_model.py:157-176), never differentiated.
+    # A missed ray's colour is its background: ray_miss never carries a gradient, whatever its weight;
+    # coarse_raycolor does once its weight is not 0.
     with torch.no_grad():
         l_miss = torch.sum(se * (1 - wm)) / 3
+        l_all = se.mean()
+    if opts.color_weights[2] != 0:
         l_all = se.mean()
     # zero_one_loss on conf_coefficient (:607-614) over the reference's dense [R'', SR, K] tensor
     # (point_aggregators.py:951-958): every (slot, k) of a valid ray, where empty slots and masked
@@ -330,9 +352,14 @@ def composite_losses(points, q, feat, valid, campos, rot, raydir, gt, opts: HotP
     wr = ray_mask.to(val.dtype)[:, None, None]
     n_e = wr.sum() * (SR * K)
     l_zo = torch.sum((torch.log(val) + torch.log(1 - val)) * wr) / torch.clamp(n_e, min=1.0)
-    total = l_col + 3e-6 + zero_one_weight * l_zo
-    parts = {"ray_masked_coarse_raycolor": l_col.detach(), "ray_miss_coarse_raycolor": l_miss,
-             "coarse_raycolor": l_all, "conf_coefficient": l_zo.detach()}
+    terms = {"ray_masked_coarse_raycolor": l_col, "ray_miss_coarse_raycolor": l_miss, "coarse_raycolor": l_all,
+             "conf_coefficient": l_zo}
+    if opts.sparse_loss_weight > 0:   # the sparse loss on conf (:652-662): the weights are detached, empty entries weigh 0
+        wn = neighbour_weights(points.xyz, q["samp_locw"], pidx)
+        wd = torch.zeros(Rd, SR, K, device=dev, dtype=wn.dtype).index_put((sr, slot), wn)[:R] * wr
+        terms["sparse"] = torch.sum(wd * torch.abs(1 - torch.exp(-2 * cc))) / (torch.sum(wd) + 1e-6)
+    total = opts.total_loss(terms, zero_one_weight=zero_one_weight)
+    parts = {k: v.detach() for k, v in terms.items()}
     if depth is None:
         return total, parts, full, ray_mask
     w = o * acc

@@ -290,14 +290,15 @@ class F16Step:
         dal = col.dfeat[samp.long(), 0]      # per item (padding: the zero row Sc)
         scale = self._loss_scale(dfs, dal)
         losses = col.losses
-        total = losses[0] + 3e-6 + 1e-4 * losses[1]
-        names = ["ray_masked_coarse_raycolor", "ray_miss_coarse_raycolor", "coarse_raycolor", "conf_coefficient"]
-        scalars = [total, losses[0], losses[2], losses[3], losses[1]]
+        o = self.tr.opts
+        parts = {"ray_masked_coarse_raycolor": losses[0], "ray_miss_coarse_raycolor": losses[2],
+                 "coarse_raycolor": losses[3], "conf_coefficient": losses[1]}
         if st["depth"] is not None:
-            scalars[0] = total + st["depth"].weight * losses[7]
-            scalars.append(losses[7])
-            names.append("coarse_depth")
-        return {"scalars": torch.stack(scalars), "names": names,
+            parts["coarse_depth"] = losses[7]
+        if o.sparse_loss_weight > 0:
+            parts["sparse"] = losses[8]
+        total = o.total_loss(parts, None if st["depth"] is None else st["depth"].weight)
+        return {"scalars": torch.stack([total] + list(parts.values())), "names": list(parts),
                 "full": col.full[:st["R"]], "ray_mask": col.mask[:st["R"]], "dfs": dfs, "dal": dal, "scale": scale}
 
     def _graph_losses(self, b, S, n):

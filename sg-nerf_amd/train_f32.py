@@ -155,12 +155,16 @@ class ColourStage:
         self.h = [torch.empty(cap, 128, **f32) for _ in range(3)]       # colour h1, h2, h3
         self.dy = [torch.empty(cap, 128, **f32) for _ in range(3)]      # colour dy1, dy2, dy3
         self.dfs = torch.empty(cap, 256, **f32)
-        self.losses = torch.zeros(8, **f32)
+        # the loss vector: 8 floats of the stock entries, 12 of sgn_loss_train_opts (another objective than ScanNet's)
+        self.lo = trainer._loss_opts()
+        K = trainer.opts.K
+        self.losses = torch.zeros(8 if self.lo is None else 12, **f32)
         self.full = torch.empty(max(R, 1), 3, **f32)
         self.mask = torch.empty(max(R, 1), dtype=torch.int8, device=dev)
         # sized for the depth-supervised stage too (R floats and a few partial sums more)
-        self.loss_ws = torch.empty(max(int(L.sgn_loss_depth_workspace_bytes(R, trainer.opts.SR)), 16),
-                                   dtype=torch.uint8, device=dev)
+        self.loss_ws = torch.empty(max(int(L.sgn_loss_depth_workspace_bytes(R, trainer.opts.SR)),
+                                       0 if self.lo is None else int(L.sgn_loss_opts_workspace_bytes(R, trainer.opts.SR, K)),
+                                       16), dtype=torch.uint8, device=dev)
         self.depth = None   # [R] the depth map, allocated by the first depth-supervised step
         self.part_col = [torch.empty(SPLITS_ITEMS, 128, n, **f32) for n in (129, 129, 281)]
         self.part_c6 = torch.empty(int(L.sgn_train_head_partial_floats(0)), **f32)
@@ -214,7 +218,8 @@ class ColourStage:
 
     def forward_and_loss(self, campos, rot, gt, lp, st, depth=None):
         """Colour forward into feat[.].yzw, then the losses, on stream st: the loss vector (sgn_loss_train's
-        8 floats), full [R, 3] and mask [R] (int8) land in self.losses / full / mask, d feat in self.dfeat.
+        8 floats; sgn_loss_train_opts' 12 under other loss options than ScanNet's, which the trainer's
+        _loss_opts() selects), full [R, 3] and mask [R] (int8) land in self.losses / full / mask, d feat in self.dfeat.
         depth (a train.DepthTarget): sgn_loss_train_depth instead -- L_depth in losses[7], the depth map in
         self.depth, d feat with the depth term."""
         L = _lib.lib()
@@ -227,14 +232,19 @@ class ColourStage:
         args = (p(campos), p(rot), self.R, ctypes.byref(self.qo), p(self.feat), p(gt), p(P.points_conf), p(self.full),
                 p(self.mask), p(self.losses), p(self.dfeat), p(P.points_conf.grad), p(self.loss_ws),
                 self.loss_ws.numel(), st)
-        if depth is None:
+        dp = None
+        if depth is not None:
+            if self.depth is None:
+                self.depth = torch.empty(max(self.R, 1), dtype=torch.float32, device=self.full.device)
+            dp = _lib.LossDepth(depth.gt.data_ptr(), None if depth.mask is None else depth.mask.data_ptr(), depth.weight,
+                                self.depth.data_ptr())
+        if self.lo is not None:   # the driver's loss options: L_sparse in losses[8]
+            ck(L.sgn_loss_train_opts(ctypes.byref(lp), ctypes.byref(self.lo), None if dp is None else ctypes.byref(dp),
+                                     *args), "sgn_loss_train_opts")
+        elif dp is None:
             ck(L.sgn_loss_train(ctypes.byref(lp), *args), "sgn_loss_train")
-            return
-        if self.depth is None:
-            self.depth = torch.empty(max(self.R, 1), dtype=torch.float32, device=self.full.device)
-        dp = _lib.LossDepth(depth.gt.data_ptr(), None if depth.mask is None else depth.mask.data_ptr(), depth.weight,
-                            self.depth.data_ptr())
-        ck(L.sgn_loss_train_depth(ctypes.byref(lp), ctypes.byref(dp), *args), "sgn_loss_train_depth")
+        else:
+            ck(L.sgn_loss_train_depth(ctypes.byref(lp), ctypes.byref(dp), *args), "sgn_loss_train_depth")
 
     def backward(self, st):
         """d feat -> d f_s (self.dfs) and the colour layers' weight-gradient partials, on stream st."""
@@ -491,10 +501,12 @@ class F32Runner:
             segs.append((self.step.colour.depth[:R], b.depth_map))
         _lib.copy_segments(segs)
         parts = {"ray_masked_coarse_raycolor": lo[0], "ray_miss_coarse_raycolor": lo[2],
-                 "coarse_raycolor": lo[3], "conf_coefficient": lo[1], "total": lo[0] + 3e-6 + 1e-4 * lo[1]}
+                 "coarse_raycolor": lo[3], "conf_coefficient": lo[1]}
+        if tr.opts.sparse_loss_weight > 0:
+            parts["sparse"] = lo[8]
         if b.depth is not None:
             parts["coarse_depth"] = lo[7]
-            parts["total"] = parts["total"] + b.depth.weight * lo[7]
+        parts["total"] = tr.opts.total_loss(parts, None if b.depth is None else b.depth.weight)
         return parts, full_o, mask_o
 
     def dp_rows(self):

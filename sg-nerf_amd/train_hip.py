@@ -27,7 +27,9 @@ sgn_adam_step_multi, the points' on the row-sparse exact sgn_adam_rows (PointAda
 bit-identical to the dense update, applied at the next step's launch or at a flush).  The plane
 background model's per-ray colour (inputs['bg_ray']) enters the loss stage as T_bg * bg_ray.  Depth
 supervision (`depth=`, a train.DepthTarget) switches the loss stage to sgn_loss_train_depth on every path;
-without it the stock entry runs as before.
+without it the stock entry runs as before.  The objective follows opts.color_loss_items / color_loss_weights,
+zero_one_loss_items / zero_one_loss_weights, zero_epsilon and sparse_loss_weight (base_rendering_model.py:534-664):
+anything but the ScanNet colour weights without a sparse loss runs sgn_loss_train_opts.
 
 Which point tensors train follows opts.feat_grad / color_grad / dir_grad / conf_grad (neural_points.py:410-416):
 a frozen tensor's gradient pointer is NULL at the C ABI (no kernel computes it), it is in no point-Adam group
@@ -259,10 +261,19 @@ class HipTrainer:
         lp.vsize_z, lp.raydist_mode_unit = float(o.vsize[2]), int(o.raydist_mode_unit)
         for i in range(3):
             lp.bg[i] = 1.0
-        lp.zero_one_weight, lp.zero_one_eps = 1e-4, 1e-3   # train_ft: zero_one weight 1e-4, epsilon 1e-3
+        # opt.zero_one_loss_weights / zero_epsilon (train_ft: weight 1e-4, epsilon 1e-3)
+        lp.zero_one_weight, lp.zero_one_eps = o.zero_one_weight, float(o.zero_epsilon)
         if bg_ray is not None:   # per-ray background [R, 3] (device, contiguous)
             lp.bg_ray = bg_ray.data_ptr()
         return lp
+
+    def _loss_opts(self):
+        """The loss stage's options (sgn_loss_train_opts: the colour weights, the sparse loss and the points'
+        xyz its neighbour weights are restated from), or None: the ScanNet objective on the stock entries."""
+        o = self.opts
+        if o.stock_loss:
+            return None
+        return _lib.LossOpts(*o.color_weights, float(o.sparse_loss_weight), self.points.xyz.data_ptr())
 
     def backward(self, campos, rot, raydir, near, far, gt, labels=None, bg_ray=None, depth=None):
         """Forward + backward + gradient all-reduce (no parameter update).  labels: (point_labels,
