@@ -1,17 +1,13 @@
 // composite.hip -- per-ray ray_dist + front-to-back alpha composite + background fill.
 //
-// Replaces, for one ray r (sample slots 0..SR-1, selected samples first, then the
-// zero-position padding slots of sample_loc_tensor, worldcoords.py:835):
-//   ray_dist        neural_points_volumetric_model.py:569-577 (cummax of pers z, last
-//                   interval vsize[2], raydist_mode_unit replacement, * ray_valid)
-//   ray_march       diff_ray_marching.py:509-555 with alpha_blend / radiance_render
-//                   (diff_render_func.py:36-49): o = 1 - exp(-sigma*dist),
-//                   T = exclusive cumprod(1 - o + 1e-10), rgb = sum o*T*c + bg*T_last
+// For one ray r the slot walk (ray_dist, ray_march's opacity and transmittance) is ray_walk.h's; here
+//   radiance_render diff_render_func.py:36-49: rgb = sum o*T*c + bg*T_last
 //   fill_invalid    neural_points_volumetric_model.py:158-195 (rays without a valid
 //                   sample get bg, coarse_is_background 1, ray_mask 0)
 // One thread per ray, single pass over the slots (running cummax, running T).
 #include <type_traits>
 
+#include "ray_walk.h"
 #include "sgn_common.h"
 
 namespace sgn {
@@ -31,11 +27,6 @@ struct CompArgs {
 struct CompDepthArgs : CompArgs {
     float *out_depth;
 };
-
-__device__ __forceinline__ float pers_z(const float *campos, const float *rot, float x, float y, float z) {
-    float sx = __fsub_rn(x, campos[0]), sy = __fsub_rn(y, campos[1]), sz = __fsub_rn(z, campos[2]);
-    return __fadd_rn(__fadd_rn(__fmul_rn(sx, rot[2]), __fmul_rn(sy, rot[5])), __fmul_rn(sz, rot[8]));
-}
 
 // One wave = 64 rays (lane = ray).  A ray's loop stops after its last selected sample: every
 // later slot is a padding slot (sigma 0), whose opacity is exactly 0 and whose transmittance
@@ -89,13 +80,8 @@ __global__ __launch_bounds__(COMP_RAYS) void k_composite(std::conditional_t<DEPT
     float4 pf = make_float4(0.f, 0.f, 0.f, 0.f);
     float pz = 0.f, dW = 0.f, dA = 0.f;  // DEPTH: slot s-1's z, the running sums
     int c0 = 0;  // the chunk being staged: slot s lands at column s - c0
-    auto process = [&](int slot, float dist) {
-        const bool mask = dist < 1e-8f || (a.unit && dist > 2.f * a.vz);
-        dist = mask ? a.vz : dist;
-        const float valid = pv ? 1.f : 0.f;
-        dist = dist * valid;
-        const float sigma = (pv ? pf.x : 0.f) * valid;
-        const float o = 1.f - expf(-sigma * dist);
+    auto process = [&](int slot, float raw) {  // feat is loaded, and colour accumulated, for valid samples only
+        const float o = close_slot(raw, pv, pv ? pf.x : 0.f, a.vz, a.unit).o;
         const float wgt = o * T;
         if (pv) {
             cr += pf.y * wgt;
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(COMP_RAYS) void k_composite(std::conditional_t<DEPT
             }
         }
         if (want_b) sb[slot - c0] = wgt;
-        T = T * (1.f - o + 1e-10f);
+        T = trans_step(T, o);
         if (want_o) so[slot - c0] = o;
     };
     // iteration s reads slot s and closes slot s - 1's interval; slot ns (padding, z0) closes the last
@@ -118,12 +104,13 @@ __global__ __launch_bounds__(COMP_RAYS) void k_composite(std::conditional_t<DEPT
         float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
         if (s < ns) {
             const int64_t id = off + s;
-            z = pers_z(a.campos, a.rot, a.samp_locw[id * 3], a.samp_locw[id * 3 + 1], a.samp_locw[id * 3 + 2]);
+            z = sample_z(a.campos, a.rot, a.samp_locw, id);
             v = a.samp_nnb[id] > 0;
             if (v) f = *(const float4 *)(a.feat + id * 4);
         }
-        const float cm = s == 0 ? z : fmaxf(prev_cm, z);
-        if (s > 0) process(s - 1, cm - prev_cm);
+        float raw;
+        const float cm = cummax_step(s, prev_cm, z, raw);
+        if (s > 0) process(s - 1, raw);
         prev_cm = cm;
         pv = v;
         pf = f;
@@ -178,8 +165,7 @@ __global__ __launch_bounds__(256) void k_ray_march_dense(MarchArgs a) {
         const int64_t i = r * a.SR + s;
         const float v = a.valid[i] ? 1.f : 0.f;
         const float4 f = *(const float4 *)(a.feat + i * 4);
-        const float sigma = f.x * v;
-        const float o = 1.f - expf(-sigma * a.ray_dist[i]);
+        const float o = opacity(f.x * v, a.ray_dist[i]).o;
         const float wgt = o * T;
         cr += f.y * wgt;
         cg += f.z * wgt;
@@ -187,7 +173,7 @@ __global__ __launch_bounds__(256) void k_ray_march_dense(MarchArgs a) {
         a.opacity[i] = o;
         a.acc_t[i] = T;
         a.blendw[i] = wgt;
-        T = T * (1.f - o + 1e-10f);
+        T = trans_step(T, o);
     }
     a.bgT[r] = T;
     a.rgb[r * 3 + 0] = cr + (a.has_bg ? a.bg0 * T : 0.f);
@@ -283,13 +269,12 @@ struct TierArgs {
 
 constexpr int TIER_TPB = 256;
 
-// One thread per ray.  T over the closed slots [0, lo) is k_composite's arithmetic, operation for
-// operation (pers_z, running cummax, the distance replacement, o = 1 - expf(-sigma dist),
-// T *= 1 - o + 1e-10f; a slot >= ray_ns is padding, whose factor rounds to 1.0f), so the ray this
-// kernel finishes is a ray whose composite reaches slot lo with that same T.  lo < SR: no closed slot
-// is a full ray's last one (interval vsize_z).  A live ray's valid samples of [lo, hi) go to the work
-// list -- the wave's counts are scanned and one lane draws the wave's range with one atomic -- a
-// finished ray's get feat 0 (alpha 0: opacity exactly 0, transmittance factor 1.0f).
+// One thread per ray.  T over the closed slots [0, lo) is k_composite's: both walk with ray_walk.h (a slot
+// >= ray_ns is padding, whose factor rounds to 1.0f), so the ray this kernel finishes is a ray whose
+// composite reaches slot lo with that same T.  lo < SR: no closed slot is a full ray's last one (interval
+// vsize_z).  A live ray's valid samples of [lo, hi) go to the work list -- the wave's counts are scanned and
+// one lane draws the wave's range with one atomic -- a finished ray's get feat 0 (alpha 0: opacity exactly 0,
+// transmittance factor 1.0f).
 __global__ __launch_bounds__(TIER_TPB) void k_early_stop_tier(TierArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * TIER_TPB + threadIdx.x;
@@ -305,24 +290,14 @@ __global__ __launch_bounds__(TIER_TPB) void k_early_stop_tier(TierArgs a) {
     const int nclose = a.lo < ns ? a.lo : ns;
     if (nclose > 0) {
         const float z0 = pers_z(a.campos, a.rot, 0.f, 0.f, 0.f);
-        auto z_at = [&](int s) {
-            if (s >= ns) return z0;
-            const int64_t id = off + s;
-            return pers_z(a.campos, a.rot, a.samp_locw[id * 3], a.samp_locw[id * 3 + 1], a.samp_locw[id * 3 + 2]);
-        };
+        auto z_at = [&](int s) { return s >= ns ? z0 : sample_z(a.campos, a.rot, a.samp_locw, off + s); };
         float prev_cm = z_at(0);
         for (int s = 0; s < nclose; ++s) {  // slot s: the interval up to slot s + 1's cummax
-            const float cm = fmaxf(prev_cm, z_at(s + 1));
-            float dist = cm - prev_cm;
+            float raw;
+            const float cm = cummax_step(s + 1, prev_cm, z_at(s + 1), raw);
             const int64_t id = off + s;
             const bool v = a.samp_nnb[id] > 0;
-            const bool mask = dist < 1e-8f || (a.unit && dist > 2.f * a.vz);
-            dist = mask ? a.vz : dist;
-            const float valid = v ? 1.f : 0.f;
-            dist = dist * valid;
-            const float sigma = (v ? a.feat[id * 4] : 0.f) * valid;
-            const float o = 1.f - expf(-sigma * dist);
-            T = T * (1.f - o + 1e-10f);
+            T = trans_step(T, close_slot(raw, v, v ? a.feat[id * 4] : 0.f, a.vz, a.unit).o);
             prev_cm = cm;
         }
     }

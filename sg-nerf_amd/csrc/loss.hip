@@ -1,5 +1,6 @@
 // loss.hip -- the training step's per-ray loss stage, forward and backward, on the device:
-// ray_dist + ray_march + fill_invalid (as composite.hip), the masked colour MSE and the zero-one
+// ray_dist + ray_march (ray_walk.h's slot walk, as k_composite: the colour is the renderer's, bit for bit) +
+// fill_invalid (as composite.hip), the masked colour MSE and the zero-one
 // loss on the neighbours' confidence, and their gradients w.r.t. the per-sample features
 // (alpha, r, g, b) and the points' conf.  Replaces the torch autograd of:
 //   ray_dist          neural_points_volumetric_model.py:569-577
@@ -43,6 +44,7 @@
 //                   stock instantiations.
 #include <type_traits>
 
+#include "ray_walk.h"
 #include "sgn_common.h"
 
 namespace sgn {
@@ -105,11 +107,6 @@ __device__ __forceinline__ void ray_bg(const LossArgs &a, int64_t r, float (&bg)
     }
 }
 
-__device__ __forceinline__ float pers_z(const float *campos, const float *rot, float x, float y, float z) {
-    const float sx = __fsub_rn(x, campos[0]), sy = __fsub_rn(y, campos[1]), sz = __fsub_rn(z, campos[2]);
-    return __fadd_rn(__fadd_rn(__fmul_rn(sx, rot[2]), __fmul_rn(sy, rot[5])), __fmul_rn(sz, rot[8]));
-}
-
 // zero-one term of one (slot, k) entry and its derivative w.r.t. the gathered conf (the straight-
 // through clamp passes the gradient unchanged, point_aggregators.py:863-865)
 __device__ __forceinline__ float clamped_conf(float cd) {
@@ -141,15 +138,9 @@ __device__ void ray_forward(const LossArgs &a, int64_t r, bool store, float (&co
     float4 pf = make_float4(0.f, 0.f, 0.f, 0.f);
     float pz = 0.f;  // DEPTH: slot s - 1's z
     if constexpr (DEPTH) dW = dA = 0.f;
-    auto process = [&](int slot, float dist) {
-        const bool mask = dist < 1e-8f || (a.unit && dist > 2.f * a.vz);
-        dist = mask ? a.vz : dist;
-        const float valid = pv ? 1.f : 0.f;
-        dist = dist * valid;
-        const float sigma = pf.x * valid;
-        const float e = expf(-sigma * dist);
-        const float o = 1.f - e;
-        const float wgt = o * T;
+    auto process = [&](int slot, float raw) {  // every sample's feat is loaded (zeros without neighbours)
+        const SlotClose c = close_slot(raw, pv, pf.x, a.vz, a.unit);
+        const float wgt = c.o * T;
         col[0] += pf.y * wgt;
         col[1] += pf.z * wgt;
         col[2] += pf.w * wgt;
@@ -159,10 +150,10 @@ __device__ void ray_forward(const LossArgs &a, int64_t r, bool store, float (&co
         }
         if (STORE && store) {
             ws[3 * slot + 0] = T;
-            ws[3 * slot + 1] = e;
-            ws[3 * slot + 2] = dist;
+            ws[3 * slot + 1] = c.e;
+            ws[3 * slot + 2] = c.dist;
         }
-        T = T * (1.f - o + 1e-10f);
+        T = trans_step(T, c.o);
     };
     const int last = ns < SR ? ns : SR - 1;
     for (int s = 0; s <= last; ++s) {
@@ -171,12 +162,13 @@ __device__ void ray_forward(const LossArgs &a, int64_t r, bool store, float (&co
         float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
         if (s < ns) {
             const int64_t id = off + s;
-            z = pers_z(a.campos, a.rot, a.samp_locw[id * 3], a.samp_locw[id * 3 + 1], a.samp_locw[id * 3 + 2]);
+            z = sample_z(a.campos, a.rot, a.samp_locw, id);
             v = a.samp_nnb[id] > 0;
             f = *(const float4 *)(a.feat + id * 4);  // zero features for samples without neighbours
         }
-        const float cm = s == 0 ? z : fmaxf(prev_cm, z);
-        if (s > 0) process(s - 1, cm - prev_cm);
+        float raw;
+        const float cm = cummax_step(s, prev_cm, z, raw);
+        if (s > 0) process(s - 1, raw);
         prev_cm = cm;
         pv = v;
         pf = f;
@@ -355,10 +347,7 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(loss_args_t<DEPTH, SPARSE
         const float *ws = a.slot_ws + r * (int64_t)SR * 3;
         // T after every slot (the padding slots' factors are exactly 1): from the last slot
         float Tend = 1.f;
-        if (nv > 0) {
-            const float Tl = ws[3 * (nv - 1)], el = ws[3 * (nv - 1) + 1];
-            Tend = Tl * (1.f - (1.f - el) + 1e-10f);
-        }
+        if (nv > 0) Tend = trans_step(ws[3 * (nv - 1)], 1.f - ws[3 * (nv - 1) + 1]);
         // U = sum over later slots of g . c_i o_i T_i + g . bg T_end (d L / d a_s times a_s), from the end
         float bg[3];
         ray_bg(a, r, bg);
@@ -379,13 +368,10 @@ __global__ __launch_bounds__(LOSS_TPB) void k_loss_bwd(loss_args_t<DEPTH, SPARSE
             float gc = g[0] * f.y + g[1] * f.z + g[2] * f.w;
             if constexpr (DEPTH) {
                 if (gD != 0.f) {
-                    const float z = pers_z(a.campos, a.rot, a.samp_locw[id * 3], a.samp_locw[id * 3 + 1],
-                                           a.samp_locw[id * 3 + 2]);
-                    gc += gD * ((z - Dr) / Wd);
+                    gc += gD * ((sample_z(a.campos, a.rot, a.samp_locw, id) - Dr) / Wd);
                 }
             }
-            const float av = 1.f - o + 1e-10f;
-            const float dO = gc * T - U / av;               // d L / d o_s
+            const float dO = gc * T - U / trans_factor(o);  // d L / d o_s
             const bool v = a.samp_nnb[id] > 0;
             const float dsig = dO * e * dist;              // o = 1 - exp(-sigma dist)
             const float w = o * T;

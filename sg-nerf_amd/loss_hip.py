@@ -12,6 +12,9 @@ The objective follows the options' colour items and weights, zero-one weight and
 (base_rendering_model.py:534-664).  The ScanNet colour weights without a sparse loss run the stock entries as
 before; anything else runs sgn_loss_train_opts with the real weights, whose gradients are d total / d feat and
 d total / d conf as they stand.
+
+This module owns the stage's call path for every HIP step (train_f32.ColourStage, F32Runner, train_f16.F16Step):
+the argument structs, the workspace size, the entry choice (loss_train) and the loss vector's names (loss_parts).
 """
 import ctypes
 
@@ -20,8 +23,70 @@ import torch
 from . import _lib
 from .opts import HotPathOpts
 
-_N_LOSS = 8
-_N_LOSS_OPTS = 12   # sgn_loss_train_opts: + L_sparse, its gradient scale, sum of the weights, spare
+
+def loss_params(opts: HotPathOpts, bg=(1.0, 1.0, 1.0), bg_ray=None, zero_one_weight=None, zero_eps=None):
+    """sgn_loss_params from the options.  bg_ray: the rays' background [R, 3] (device fp32, contiguous; replaces bg).
+    zero_one_weight / zero_eps: None reads opts.zero_one_weight / zero_epsilon (train_ft: weight 1e-4, epsilon 1e-3)."""
+    lp = _lib.LossParams()
+    lp.SR, lp.K = opts.SR, opts.K
+    lp.vsize_z, lp.raydist_mode_unit = float(opts.vsize[2]), int(opts.raydist_mode_unit)
+    lp.bg = (_lib.c_f32 * 3)(*bg)
+    lp.zero_one_weight = float(opts.zero_one_weight if zero_one_weight is None else zero_one_weight)
+    lp.zero_one_eps = float(opts.zero_epsilon if zero_eps is None else zero_eps)
+    if bg_ray is not None:
+        lp.bg_ray = bg_ray.data_ptr()
+    return lp
+
+
+def loss_opts(opts: HotPathOpts, points):
+    """sgn_loss_opts (the colour weights, the sparse loss and the points' xyz its neighbour weights are restated
+    from), or None: the ScanNet objective on the stock entries."""
+    if opts.stock_loss:
+        return None
+    return _lib.LossOpts(*opts.color_weights, float(opts.sparse_loss_weight), points.xyz.data_ptr())
+
+
+def loss_depth(depth, out_depth):
+    """sgn_loss_depth of a train.DepthTarget writing the depth map into out_depth [R], or None without one."""
+    if depth is None:
+        return None
+    return _lib.LossDepth(depth.gt.data_ptr(), None if depth.mask is None else depth.mask.data_ptr(), depth.weight,
+                          out_depth.data_ptr())
+
+
+def loss_len(lo):   # the loss vector: 8 floats, 12 of sgn_loss_train_opts (+ L_sparse, its scale, sum of weights, spare)
+    return 8 if lo is None else 12
+
+
+def workspace_bytes(R, SR, K, stock, depth):
+    """Bytes of the loss stage's workspace for the entry these settings select."""
+    L = _lib.lib()
+    return max(int(L.sgn_loss_depth_workspace_bytes(R, SR) if depth else L.sgn_loss_workspace_bytes(R, SR)),
+               0 if stock else int(L.sgn_loss_opts_workspace_bytes(R, SR, K)), 16)
+
+
+def loss_train(lp, lo, dp, *args):
+    """The loss stage's launch: sgn_loss_train_opts under loss options (lo), else sgn_loss_train_depth with depth
+    supervision (dp), else sgn_loss_train.  args: the entries' common tail, campos .. stream."""
+    L = _lib.lib()
+    if lo is not None:
+        _lib.check(L.sgn_loss_train_opts(ctypes.byref(lp), ctypes.byref(lo), None if dp is None else ctypes.byref(dp),
+                                         *args), "sgn_loss_train_opts")
+    elif dp is not None:
+        _lib.check(L.sgn_loss_train_depth(ctypes.byref(lp), ctypes.byref(dp), *args), "sgn_loss_train_depth")
+    else:
+        _lib.check(L.sgn_loss_train(ctypes.byref(lp), *args), "sgn_loss_train")
+
+
+def loss_parts(opts: HotPathOpts, losses, depth):
+    """The reported parts by name from the loss vector (any indexable of scalars); depth: the stage ran with one."""
+    parts = {"ray_masked_coarse_raycolor": losses[0], "ray_miss_coarse_raycolor": losses[2],
+             "coarse_raycolor": losses[3], "conf_coefficient": losses[1]}
+    if opts.sparse_loss_weight > 0:
+        parts["sparse"] = losses[8]
+    if depth:
+        parts["coarse_depth"] = losses[7]
+    return parts
 
 
 class _HipLoss(torch.autograd.Function):
@@ -48,19 +113,7 @@ class LossStage:
 
     def __init__(self, device):
         self.device = torch.device(device)
-        self._key = None
-
-    def _buffers(self, R, SR, depth=False, K=0):
-        """The workspace grows, never moves to a smaller one (a captured graph keeps the pointer it
-        was captured with: HipTrainer gives every captured loss stage its own LossStage)."""
-        L = _lib.lib()
-        need = max(int(L.sgn_loss_depth_workspace_bytes(R, SR) if depth else L.sgn_loss_workspace_bytes(R, SR)), 16)
-        if K:   # sgn_loss_train_opts
-            need = max(need, int(L.sgn_loss_opts_workspace_bytes(R, SR, K)))
-        if self._key is None or self.ws.numel() < need:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._key = (R, SR)
-        return self.ws
+        self.ws = None
 
     def __call__(self, points, q_abi, feat, campos, rot, gt, opts: HotPathOpts, R, bg=(1.0, 1.0, 1.0),
                  zero_one_weight=None, zero_eps=None, bg_ray=None, depth=None):
@@ -78,59 +131,37 @@ class LossStage:
         feat = feat.contiguous()
         if feat.shape[0] == 0:   # a batch without samples: one zero row keeps the pointers valid
             feat = torch.cat([feat, feat.new_zeros(1, 4)])
-        stock = opts.stock_loss
+        lo = loss_opts(opts, points)
+        stock = lo is None
         zero_one_weight = opts.zero_one_weight if zero_one_weight is None else zero_one_weight
-        zero_eps = opts.zero_epsilon if zero_eps is None else zero_eps
-        ws = self._buffers(R, opts.SR, depth is not None, 0 if stock else opts.K)
+        need = workspace_bytes(R, opts.SR, opts.K, stock, depth is not None)
+        if self.ws is None or self.ws.numel() < need:   # the workspace grows, never moves to a smaller one
+            self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         campos = campos.reshape(3).to(dev, torch.float32).contiguous()
         rot = rot.reshape(3, 3).to(dev, torch.float32).contiguous()
         gt = gt.reshape(-1, 3).to(dev, torch.float32).contiguous()
-        lp = _lib.LossParams()
-        lp.SR, lp.K = opts.SR, opts.K
-        lp.vsize_z, lp.raydist_mode_unit = float(opts.vsize[2]), int(opts.raydist_mode_unit)
-        for i in range(3):
-            lp.bg[i] = float(bg[i])
-        # stock: dconf = d zero-one / d conf, weighted by autograd; else the kernel weighs every term
-        lp.zero_one_weight, lp.zero_one_eps = 1.0 if stock else float(zero_one_weight), float(zero_eps)
-        lo = None if stock else _lib.LossOpts(*opts.color_weights, float(opts.sparse_loss_weight),
-                                              points.xyz.data_ptr())
         if bg_ray is not None:
             bg_ray = bg_ray.reshape(R, 3).to(dev, torch.float32).contiguous()
-            lp.bg_ray = bg_ray.data_ptr()
-        dmap = None
-        if depth is not None:
-            dmap = torch.empty(R, dtype=torch.float32, device=dev)
-            dp = _lib.LossDepth(depth.gt.data_ptr(), None if depth.mask is None else depth.mask.data_ptr(),
-                                depth.weight, dmap.data_ptr())
+        # stock: dconf = d zero-one / d conf, weighted by autograd; else the kernel weighs every term
+        lp = loss_params(opts, bg, bg_ray, 1.0 if stock else zero_one_weight, zero_eps)
+        dmap = None if depth is None else torch.empty(R, dtype=torch.float32, device=dev)
+        dp = loss_depth(depth, dmap)
 
         def run(feat_t, conf_t):
-            losses = torch.empty(_N_LOSS if stock else _N_LOSS_OPTS, dtype=torch.float32, device=dev)
+            losses = torch.empty(loss_len(lo), dtype=torch.float32, device=dev)
             full = torch.empty(R, 3, dtype=torch.float32, device=dev)
             mask = torch.empty(R, dtype=torch.int8, device=dev)
             dfeat = torch.zeros_like(feat_t)   # entries past the rays' samples (capacity padding) stay 0
             dconf = torch.zeros(n_points, dtype=torch.float32, device=dev) if conf_t.requires_grad else None
             args = (_lib.ptr(campos), _lib.ptr(rot), R, ctypes.byref(q_abi), _lib.ptr(feat_t.detach()), _lib.ptr(gt),
                     _lib.ptr(conf_t.detach()), _lib.ptr(full), _lib.ptr(mask), _lib.ptr(losses), _lib.ptr(dfeat),
-                    _lib.ptr(dconf), _lib.ptr(ws), ws.numel(), _lib.stream_handle())
-            if not stock:
-                _lib.check(_lib.lib().sgn_loss_train_opts(ctypes.byref(lp), ctypes.byref(lo),
-                                                          None if depth is None else ctypes.byref(dp), *args),
-                           "sgn_loss_train_opts")
-            elif depth is None:
-                _lib.check(_lib.lib().sgn_loss_train(ctypes.byref(lp), *args), "sgn_loss_train")
-            else:
-                _lib.check(_lib.lib().sgn_loss_train_depth(ctypes.byref(lp), ctypes.byref(dp), *args),
-                           "sgn_loss_train_depth")
+                    _lib.ptr(dconf), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_handle())
+            loss_train(lp, lo, dp, *args)
             return losses, full, mask, dfeat, None if dconf is None else dconf.view(conf_t.shape)
 
         losses, full, mask = _HipLoss.apply(feat, conf, run, not stock)
         l_col, l_zo = losses[0], losses[1]
-        parts = {"ray_masked_coarse_raycolor": l_col.detach(), "ray_miss_coarse_raycolor": losses[2].detach(),
-                 "coarse_raycolor": losses[3].detach(), "conf_coefficient": l_zo.detach()}
-        if opts.sparse_loss_weight > 0:
-            parts["sparse"] = losses[8].detach()
-        if depth is not None:
-            parts["coarse_depth"] = losses[7].detach()   # its gradient is in d feat already
+        parts = loss_parts(opts, losses.detach(), depth is not None)   # coarse_depth's gradient is in d feat already
         if stock:
             total = opts.total_loss({**parts, "ray_masked_coarse_raycolor": l_col, "conf_coefficient": l_zo},
                                     zero_one_weight=zero_one_weight)

@@ -11,7 +11,7 @@ epilogue (all-reduce, point-row exchange):
                  row layers' inputs saved
     colour+loss  one captured HIP graph per capacity bucket (sgn_colour_inputs, train_f32.ColourStage
                  with one fp16 product per backward multiply-add, its sgn_reduce_partials,
-                 sgn_pow2_scale), or the same stage eagerly (HipTrainer.use_graph = False) through
+                 sgn_pow2_scale; the results out through ColourStage.results_out), or the same stage eagerly (HipTrainer.use_graph = False) through
                  loss_hip.LossStage and torch autograd of the colour MLP -- the graph's parity
                  reference in the tests
     backward     sgn_aggregate_backward (k_agg_bwd): deltas of the 4 row layers, d alpha-logit, point
@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .flat_mlp import _colmap
-from .loss_hip import LossStage
+from .loss_hip import LossStage, loss_parts
 from .train import DepthTarget, _pe, gather_counts, touched_rows
 from .train_f32 import ColourStage, _attach_bpack
 from .weights import BPNET
@@ -282,24 +282,16 @@ class F16Step:
                                        _lib.ptr(col.vpe), stream), "sgn_colour_inputs")
         # hand-written colour MLP, losses and backward (train_f32.ColourStage), its weight gradients reduced
         st["amax"].zero_()
-        col.forward_and_loss(st["campos"], st["rot"], st["gt"], self.tr._loss_params(st["bg_ray"]), stream,
-                             st["depth"])
+        col.forward_and_loss(st["campos"], st["rot"], st["gt"], st["bg_ray"], stream, st["depth"])
         col.backward(stream)
         _lib.check(L.sgn_reduce_partials(len(st["segs"]), st["segs"], stream), "sgn_reduce_partials")
         dfs = col.dfs
         dal = col.dfeat[samp.long(), 0]      # per item (padding: the zero row Sc)
         scale = self._loss_scale(dfs, dal)
-        losses = col.losses
-        o = self.tr.opts
-        parts = {"ray_masked_coarse_raycolor": losses[0], "ray_miss_coarse_raycolor": losses[2],
-                 "coarse_raycolor": losses[3], "conf_coefficient": losses[1]}
-        if st["depth"] is not None:
-            parts["coarse_depth"] = losses[7]
-        if o.sparse_loss_weight > 0:
-            parts["sparse"] = losses[8]
-        total = o.total_loss(parts, None if st["depth"] is None else st["depth"].weight)
+        parts = loss_parts(self.tr.opts, col.losses, st["depth"] is not None)
+        total = self.tr.opts.total_loss(parts, None if st["depth"] is None else st["depth"].weight)
         return {"scalars": torch.stack([total] + list(parts.values())), "names": list(parts),
-                "full": col.full[:st["R"]], "ray_mask": col.mask[:st["R"]], "dfs": dfs, "dal": dal, "scale": scale}
+                "dfs": dfs, "dal": dal, "scale": scale}
 
     def _graph_losses(self, b, S, n):
         """Replay the captured loss stage for this step's capacity bucket (item / sample counts
@@ -378,19 +370,11 @@ class F16Step:
                            ([] if depth is None or depth.mask is None else [(depth.mask, st["depth"].mask)]))
         st["graph"].replay()
         out = st["out"]
-        # the loss, its parts, the rendered colour and the ray mask out of the graph's buffers: one
-        # launch into one fresh allocation (the caller may keep them across steps)
-        nsc = out["scalars"].numel()
-        o_full = 8 * (-(-nsc // 8))
-        nm = -(-R // 4)
-        buf = torch.empty(o_full + 3 * R + nm + (R if depth is not None else 0), dtype=torch.float32, device=dev)
-        sc, full = buf[:nsc], buf[o_full:o_full + 3 * R].view(R, 3)
-        ray_mask = buf[o_full + 3 * R:o_full + 3 * R + nm].view(torch.bool)[:R]
-        dmap = buf[o_full + 3 * R + nm:] if depth is not None else None
-        _lib.copy_segments([(out["scalars"], sc), (out["full"], full), (out["ray_mask"], ray_mask)] +
-                           ([] if depth is None else [(st["col"].depth[:R], dmap)]))
+        # the loss, its parts, the rendered colour and the ray mask out of the graph's buffers (the caller may
+        # keep them across steps)
+        sc, full, ray_mask, dmap = st["col"].results_out(out["scalars"], depth is not None)
         return {"total": sc[0], "parts": {k: sc[1 + i] for i, k in enumerate(out["names"])},
-                "full": full, "ray_mask": ray_mask, "depth": dmap,
+                "full": full, "ray_mask": ray_mask.view(torch.bool), "depth": dmap,
                 "dfs": out["dfs"], "dal": out["dal"], "scale": out["scale"]}
 
     # -- weight gradients of the row layers ---------------------------------------------------

@@ -13,7 +13,7 @@ as one captured graph:
   sgn_train_row_inputs       x0 = [emb | PE(emb) | PE(dists) | 1], extra channels, blend weights,
                              PE(viewdir); SG: sgn_train_row_gather, the rows' BPNet embedding
   colour forward             3 x sgn_x3_gemm (x W^T + b, LeakyReLU) + sgn_train_colour_head (rgb)
-  sgn_loss_train             ray_dist + ray_march + losses and d feat, d conf (zero-one)
+  sgn_loss_train             ray_dist + ray_march + losses and d feat, d conf (zero-one); loss_hip.loss_train's entry
   colour backward            sgn_train_colour_head_bwd, 3 x dy W (masked), 3 x dy^T x (split-K)
   row backward               z4 = LReLU(z3) W3^T + b3; sgn_train_row_head (alpha, K-blend, delta4,
                              d conf); 4 x delta W (masked; SG 5); sgn_train_row_tail (d emb /
@@ -33,7 +33,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, loss_hip
 from .train import gather_counts, touched_rows
 
 # split-K partials of the weight-gradient GEMMs (rows / items cut into this many 32-aligned runs;
@@ -155,16 +155,15 @@ class ColourStage:
         self.h = [torch.empty(cap, 128, **f32) for _ in range(3)]       # colour h1, h2, h3
         self.dy = [torch.empty(cap, 128, **f32) for _ in range(3)]      # colour dy1, dy2, dy3
         self.dfs = torch.empty(cap, 256, **f32)
-        # the loss vector: 8 floats of the stock entries, 12 of sgn_loss_train_opts (another objective than ScanNet's)
-        self.lo = trainer._loss_opts()
-        K = trainer.opts.K
-        self.losses = torch.zeros(8 if self.lo is None else 12, **f32)
+        # the loss stage's options (None: the ScanNet objective on the stock entries) and its loss vector
+        o = self.opts = trainer.opts
+        self.lo = loss_hip.loss_opts(o, trainer.points)
+        self.losses = torch.zeros(loss_hip.loss_len(self.lo), **f32)
         self.full = torch.empty(max(R, 1), 3, **f32)
         self.mask = torch.empty(max(R, 1), dtype=torch.int8, device=dev)
         # sized for the depth-supervised stage too (R floats and a few partial sums more)
-        self.loss_ws = torch.empty(max(int(L.sgn_loss_depth_workspace_bytes(R, trainer.opts.SR)),
-                                       0 if self.lo is None else int(L.sgn_loss_opts_workspace_bytes(R, trainer.opts.SR, K)),
-                                       16), dtype=torch.uint8, device=dev)
+        self.loss_ws = torch.empty(loss_hip.workspace_bytes(R, o.SR, o.K, self.lo is None, True), dtype=torch.uint8,
+                                   device=dev)
         self.depth = None   # [R] the depth map, allocated by the first depth-supervised step
         self.part_col = [torch.empty(SPLITS_ITEMS, 128, n, **f32) for n in (129, 129, 281)]
         self.part_c6 = torch.empty(int(L.sgn_train_head_partial_floats(0)), **f32)
@@ -216,12 +215,11 @@ class ColourStage:
                                    128, 128)]
         self.w6, self.b6 = W("color_branch.6")[0], A.B("color_branch.6")
 
-    def forward_and_loss(self, campos, rot, gt, lp, st, depth=None):
-        """Colour forward into feat[.].yzw, then the losses, on stream st: the loss vector (sgn_loss_train's
-        8 floats; sgn_loss_train_opts' 12 under other loss options than ScanNet's, which the trainer's
-        _loss_opts() selects), full [R, 3] and mask [R] (int8) land in self.losses / full / mask, d feat in self.dfeat.
-        depth (a train.DepthTarget): sgn_loss_train_depth instead -- L_depth in losses[7], the depth map in
-        self.depth, d feat with the depth term."""
+    def forward_and_loss(self, campos, rot, gt, bg_ray, st, depth=None):
+        """Colour forward into feat[.].yzw, then the losses (loss_hip.loss_train: the entry the loss options
+        and depth select), on stream st: the loss vector, full [R, 3] and mask [R] (int8) land in self.losses /
+        full / mask, d feat in self.dfeat.  bg_ray: the rays' background [R, 3] or None (white).  depth (a
+        train.DepthTarget): L_depth in losses[7], the depth map in self.depth, d feat with the depth term."""
         L = _lib.lib()
         ck, p = _lib.check, _lib.ptr
         P = self.points
@@ -229,22 +227,27 @@ class ColourStage:
             ck(L.sgn_x3_gemm(ctypes.byref(gs), st), "sgn_x3_gemm")
         ck(L.sgn_train_colour_head(ctypes.byref(self.qo), self.n_items, p(self.h[2]), self.w6, self.b6, p(self.feat),
                                    st), "sgn_train_colour_head")
-        args = (p(campos), p(rot), self.R, ctypes.byref(self.qo), p(self.feat), p(gt), p(P.points_conf), p(self.full),
-                p(self.mask), p(self.losses), p(self.dfeat), p(P.points_conf.grad), p(self.loss_ws),
-                self.loss_ws.numel(), st)
-        dp = None
-        if depth is not None:
-            if self.depth is None:
-                self.depth = torch.empty(max(self.R, 1), dtype=torch.float32, device=self.full.device)
-            dp = _lib.LossDepth(depth.gt.data_ptr(), None if depth.mask is None else depth.mask.data_ptr(), depth.weight,
-                                self.depth.data_ptr())
-        if self.lo is not None:   # the driver's loss options: L_sparse in losses[8]
-            ck(L.sgn_loss_train_opts(ctypes.byref(lp), ctypes.byref(self.lo), None if dp is None else ctypes.byref(dp),
-                                     *args), "sgn_loss_train_opts")
-        elif dp is None:
-            ck(L.sgn_loss_train(ctypes.byref(lp), *args), "sgn_loss_train")
-        else:
-            ck(L.sgn_loss_train_depth(ctypes.byref(lp), ctypes.byref(dp), *args), "sgn_loss_train_depth")
+        if depth is not None and self.depth is None:
+            self.depth = torch.empty(max(self.R, 1), dtype=torch.float32, device=self.full.device)
+        loss_hip.loss_train(loss_hip.loss_params(self.opts, bg_ray=bg_ray), self.lo,
+                            loss_hip.loss_depth(depth, self.depth), p(campos), p(rot), self.R, ctypes.byref(self.qo), p(self.feat), p(gt), p(P.points_conf),
+                            p(self.full), p(self.mask), p(self.losses), p(self.dfeat), p(P.points_conf.grad),
+                            p(self.loss_ws), self.loss_ws.numel(), st)
+
+    def results_out(self, scalars, depth):
+        """The next step reuses the stage's buffers: scalars (the loss vector, or what was made of it), colour, mask
+        and, with depth, the depth map out into one fresh allocation by one sgn_copy_segments launch, returned."""
+        R = self.R
+        ns = scalars.numel()
+        o_full = 8 * (-(-ns // 8))
+        nm = -(-R // 4)
+        buf = torch.empty(o_full + 3 * R + nm + (R if depth else 0), dtype=torch.float32, device=scalars.device)
+        sc, full = buf[:ns], buf[o_full:o_full + 3 * R].view(R, 3)
+        mask = buf[o_full + 3 * R:o_full + 3 * R + nm].view(torch.int8)[:R]
+        dmap = buf[o_full + 3 * R + nm:] if depth else None
+        _lib.copy_segments([(scalars, sc), (self.full[:R], full), (self.mask[:R], mask)] +
+                           ([(self.depth[:R], dmap)] if depth else []))
+        return sc, full, mask, dmap
 
     def backward(self, st):
         """d feat -> d f_s (self.dfs) and the colour layers' weight-gradient partials, on stream st."""
@@ -389,11 +392,11 @@ class F32Step:
                                    A.flat.device)
 
     # -- one step ------------------------------------------------------------------------------
-    def run(self, pt, proj, blob, campos, rot, gt, lp, depth=None):
+    def run(self, pt, proj, blob, campos, rot, gt, bg_ray, depth=None):
         """Forward + backward of one batch after the query (gradients added into flat.grad and the
-        point gradients; those must be zero / as the caller wants them).  Returns the device loss
-        vector (sgn_loss_train's 8 floats), the rendered colour [R, 3] and the ray mask [R] (int8);
-        with depth (a train.DepthTarget) the depth map is in self.colour.depth."""
+        point gradients; those must be zero / as the caller wants them).  Returns fresh copies of the loss
+        vector, the rendered colour [R, 3], the ray mask [R] (int8) and, with depth (a train.DepthTarget), the
+        depth map (ColourStage.results_out)."""
         L = _lib.lib()
         st = _lib.stream_handle()
         tr, K, qo, col = self.trainer, self.K, self.qo, self.colour
@@ -416,7 +419,7 @@ class F32Step:
         if self.D:
             ck(L.sgn_train_row_gather(ctypes.byref(qo), K, p(self.row_off), p(self.counts), p(tr.bpnet32), self.D,
                                       p(self.bprow), st), "sgn_train_row_gather")
-        col.forward_and_loss(campos, rot, gt, lp, st, depth)
+        col.forward_and_loss(campos, rot, gt, bg_ray, st, depth)
         col.backward(st)
         gemm(self.g_z4)
         ck(L.sgn_train_row_head(ctypes.byref(pt), ctypes.byref(qo), K, p(self.row_off), p(self.counts), p(self.z[3]),
@@ -430,7 +433,7 @@ class F32Step:
         for gs in self.g_row_dw:
             gemm(gs)
         ck(L.sgn_reduce_partials(self.n_seg, self.segs, st), "sgn_reduce_partials")
-        return col.losses, col.full[:self.R], col.mask[:self.R]
+        return col.results_out(col.losses, depth is not None)
 
 
 class F32Runner:
@@ -443,7 +446,7 @@ class F32Runner:
               rank's touched rows, which ride the point-row exchange)
       run     sgn_point_project_f32 on a list (block1.0's per-point part for the touched points only: ~50 k
               of 1.2 M for a 4096-ray batch -- the rows read no other point, and the weights change
-              every step), F32Step.run, the results out into one fresh allocation"""
+              every step), F32Step.run, the results out into one fresh allocation (ColourStage.results_out)"""
 
     graph_captures = 0   # no captured graphs at this precision
 
@@ -486,28 +489,10 @@ class F32Runner:
         key = (R, q.work.data_ptr(), q.pidx.data_ptr(), fl.data_ptr(), fl.grad.data_ptr())
         if self.key != key:
             self.step, self.key = F32Step(tr, q, R), key
-        losses, full, mask = self.step.run(pt, self.proj, self._blob, b.campos, b.rot, b.gt, tr._loss_params(b.bg_ray),
-                                           b.depth)
-        # the step's buffers are reused by the next step: the losses, the colour and the mask out into
-        # one fresh allocation (one launch), as the f16 step's graph outputs
-        nl = losses.numel()
-        nm = -(-R // 4)
-        buf = torch.empty(nl + 3 * R + nm + (R if b.depth is not None else 0), dtype=torch.float32, device=dev)
-        lo, full_o = buf[:nl], buf[nl:nl + 3 * R].view(R, 3)
-        mask_o = buf[nl + 3 * R:nl + 3 * R + nm].view(torch.int8)[:R]
-        segs = [(losses, lo), (full, full_o), (mask, mask_o)]
-        if b.depth is not None:
-            b.depth_map = buf[nl + 3 * R + nm:]
-            segs.append((self.step.colour.depth[:R], b.depth_map))
-        _lib.copy_segments(segs)
-        parts = {"ray_masked_coarse_raycolor": lo[0], "ray_miss_coarse_raycolor": lo[2],
-                 "coarse_raycolor": lo[3], "conf_coefficient": lo[1]}
-        if tr.opts.sparse_loss_weight > 0:
-            parts["sparse"] = lo[8]
-        if b.depth is not None:
-            parts["coarse_depth"] = lo[7]
+        lo, full, mask, b.depth_map = self.step.run(pt, self.proj, self._blob, b.campos, b.rot, b.gt, b.bg_ray, b.depth)
+        parts = loss_hip.loss_parts(tr.opts, lo, b.depth is not None)
         parts["total"] = tr.opts.total_loss(parts, None if b.depth is None else b.depth.weight)
-        return parts, full_o, mask_o
+        return parts, full, mask
 
     def dp_rows(self):
         """Under DP: this rank's touched rows and every rank's count (gathered and read here: the

@@ -254,27 +254,6 @@ class HipTrainer:
             raise ValueError(f"bg_ray has {bg_ray.shape[0]} rays, the batch {R}")
         return bg_ray
 
-    def _loss_params(self, bg_ray=None):
-        o = self.opts
-        lp = _lib.LossParams()
-        lp.SR, lp.K = o.SR, o.K
-        lp.vsize_z, lp.raydist_mode_unit = float(o.vsize[2]), int(o.raydist_mode_unit)
-        for i in range(3):
-            lp.bg[i] = 1.0
-        # opt.zero_one_loss_weights / zero_epsilon (train_ft: weight 1e-4, epsilon 1e-3)
-        lp.zero_one_weight, lp.zero_one_eps = o.zero_one_weight, float(o.zero_epsilon)
-        if bg_ray is not None:   # per-ray background [R, 3] (device, contiguous)
-            lp.bg_ray = bg_ray.data_ptr()
-        return lp
-
-    def _loss_opts(self):
-        """The loss stage's options (sgn_loss_train_opts: the colour weights, the sparse loss and the points'
-        xyz its neighbour weights are restated from), or None: the ScanNet objective on the stock entries."""
-        o = self.opts
-        if o.stock_loss:
-            return None
-        return _lib.LossOpts(*o.color_weights, float(o.sparse_loss_weight), self.points.xyz.data_ptr())
-
     def backward(self, campos, rot, raydir, near, far, gt, labels=None, bg_ray=None, depth=None):
         """Forward + backward + gradient all-reduce (no parameter update).  labels: (point_labels,
         ray_labels, seconds) for the semantic-guided query (semantic_guidance = 1).  bg_ray: the

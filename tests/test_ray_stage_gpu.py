@@ -418,6 +418,90 @@ def test_composite(i):
         _ratio(full["w"][:R], ref["w"], fb["Ew"], f"{tag} blend weight")
 
 
+# ---- one walk: the loss stage's colour, mask and depth are the composite's ----------------------------
+
+def _run_walk(sc, dv, unit, bg, bg_ray):
+    """sgn_composite_depth with the constant bg, and sgn_loss_train / sgn_loss_train_depth with bg or the per-ray
+    bg_ray, on the scene's query and feat: the outputs both sides have."""
+    R, SR = sc["R"], sc["SR"]
+    p, d = _lib.ptr, dv.d
+    L, st = _lib.lib(), _lib.stream_handle()
+    f32 = dict(dtype=F32, device=DEV)
+    comp = dict(rgb=torch.full((R, 3), NAN, **f32), mask=torch.full((R,), 77, dtype=torch.int8, device=DEV),
+                bgT=torch.full((R,), NAN, **f32), depth=torch.full((R,), NAN, **f32))
+    cp = _lib.CompositeParams()
+    cp.SR, cp.vsize_z, cp.raydist_mode_unit = SR, rs.VZ, unit
+    cp.bg[0], cp.bg[1], cp.bg[2] = bg
+    stock = dict(rgb=torch.full((R, 3), NAN, **f32), mask=torch.full((R,), 77, dtype=torch.int8, device=DEV))
+    _lib.check(L.sgn_composite(ctypes.byref(cp), p(d["campos"]), p(d["rot"]), p(d["gt"]), R, None, 0, 0, ctypes.byref(dv.qo),
+                               p(d["feat"]), p(stock["rgb"]), p(stock["mask"]), None, None, None, st), "sgn_composite")
+    _lib.check(L.sgn_composite_depth(ctypes.byref(cp), p(d["campos"]), p(d["rot"]), p(d["gt"]), R, None, 0, 0,
+                                     ctypes.byref(dv.qo), p(d["feat"]), p(comp["rgb"]), p(comp["mask"]), p(comp["bgT"]), None,
+                                     None, p(comp["depth"]), st), "sgn_composite_depth")
+    lp = _lib.LossParams()
+    lp.SR, lp.K, lp.vsize_z, lp.raydist_mode_unit = SR, sc["K"], rs.VZ, unit
+    lp.bg[0], lp.bg[1], lp.bg[2] = bg
+    lp.zero_one_weight, lp.zero_one_eps = 1e-4, rs.ZO_EPS
+    lp.bg_ray = None if bg_ray is None else bg_ray.data_ptr()
+    ws = torch.empty(max(int(L.sgn_loss_depth_workspace_bytes(R, SR)), 16), dtype=torch.uint8, device=DEV)
+    gt_d = torch.ones(R, **f32)
+    loss = {}
+    for name in ("stock", "depth"):
+        o = loss[name] = dict(rgb=torch.full((R, 3), NAN, **f32), mask=torch.full((R,), 77, dtype=torch.int8, device=DEV),
+                              depth=torch.full((R,), NAN, **f32))
+        args = (p(d["campos"]), p(d["rot"]), R, ctypes.byref(dv.qo), p(d["feat"]), p(d["gt"]), p(d["conf"]), p(o["rgb"]),
+                p(o["mask"]), p(torch.empty(8, **f32)), p(torch.empty(sc["S_cap"], 4, **f32)), None, p(ws), ws.numel(), st)
+        if name == "stock":
+            _lib.check(L.sgn_loss_train(ctypes.byref(lp), *args), "sgn_loss_train")
+        else:
+            dp = _lib.LossDepth(gt_d.data_ptr(), None, 0.5, o["depth"].data_ptr())
+            _lib.check(L.sgn_loss_train_depth(ctypes.byref(lp), ctypes.byref(dp), *args), "sgn_loss_train_depth")
+    torch.cuda.synchronize()
+    cpu = lambda m: {k: v.cpu() for k, v in m.items()}  # noqa: E731
+    return cpu(stock), cpu(comp), cpu(loss["stock"]), cpu(loss["depth"])
+
+
+@pytest.mark.parametrize("bgr", [False, True])
+@pytest.mark.parametrize("unit", [0, 1])
+@pytest.mark.parametrize("SR", [5, 36])
+def test_loss_stage_walk_is_the_composites(SR, unit, bgr):
+    """The contract csrc/ray_walk.h carries: on one query and one feat (zeros at samples without neighbours)
+    sgn_loss_train's out_rgb / out_mask are sgn_composite's and sgn_loss_train_depth's out_depth is
+    sgn_composite_depth's, bit for bit.  R = 70 crosses a 64-ray composite workgroup and a 32-ray loss block;
+    SR = 5 is less than one 32-slot chunk and no multiple of 4, SR = 36 is two chunks.  With a per-ray background
+    the composite side has no matching input: it runs with bg 0 (its colour is then the bare sum, x + 0 * T = x)
+    and the loss stage's colour is that sum + bg_ray * T_end, the two roundings the kernel makes, for the rays
+    with a valid sample; the others carry bg_ray itself."""
+    R, K = 70, 3
+    sc = rs.ray_scene(R, SR, K, seed=90 + SR, camera=1 if SR == 5 else 0, **_scene_kw(SR))
+    # ---- the scene holds every case the walk distinguishes (from the inputs alone)
+    S, ns = sc["S"], sc["ray_ns"].long()
+    assert bool((sc["feat"][:S][sc["samp_nnb"][:S] == 0] == 0).all())
+    _, valid, raw = rs.ray_dist_fp32(sc, unit)
+    assert bool((ns == 0).any()) and bool((ns == SR).any()) and bool((ns == SR - 1).any())
+    assert bool(((ns > 0) & ~valid.any(dim=1)).any())                       # samples, none with a neighbour
+    c, r = sc["campos"], sc["rot"].reshape(-1)
+    pos = rs.densify(sc, sc["samp_locw"])
+    z = ((pos[..., 0] - c[0]) * r[2] + (pos[..., 1] - c[1]) * r[5]) + (pos[..., 2] - c[2]) * r[8]
+    pair = torch.arange(1, SR)[None, :] < ns[:, None]                       # slots s, s + 1 both hold a sample
+    assert bool(((z[:, 1:] == z[:, :-1]) & (raw[:, :-1] < 1e-8) & pair).any())
+    assert bool(((raw[:, :-1] > 2 * rs.VZ) & pair).any())
+    dv = Dev(sc)
+    bg = (0.0, 0.0, 0.0) if bgr else BG
+    stock, comp, loss, loss_d = _run_walk(sc, dv, unit, bg, dv.d["bg_ray"] if bgr else None)
+    mask = comp["mask"].bool()
+    assert torch.equal(mask, valid.any(dim=1)) and torch.equal(stock["mask"], comp["mask"])
+    assert _same_bits(stock["rgb"], comp["rgb"])
+    want = comp["rgb"]
+    if bgr:
+        want = torch.where(mask[:, None], comp["rgb"] + sc["bg_ray"] * comp["bgT"][:, None], sc["bg_ray"])
+    for name, out in (("sgn_loss_train", loss), ("sgn_loss_train_depth", loss_d)):
+        assert torch.equal(out["mask"], comp["mask"]), name
+        assert _same_bits(out["rgb"], want), name
+    assert _same_bits(loss_d["depth"], comp["depth"])
+    assert _all_nan(loss["depth"])
+
+
 # ---- sgn_ray_march_dense -------------------------------------------------------------------------
 
 DENSE_CASES = [(1, 1), (255, 24), (257, 33), (256, 128)]
