@@ -342,7 +342,7 @@ static int grid_build_impl(const float *d_points, int64_t n, const sgn_grid_para
     uint32_t *pslot, *skey;
     int32_t *pid, *sval, *seg_start, *seg_end, *resv;
     if (tmp.get(&pslot, n) || tmp.get(&skey, n) || tmp.get(&pid, n) || tmp.get(&sval, n) ||
-        tmp.get(&seg_start, ns) || tmp.get(&seg_end, ns) || tmp.get(&resv, ns * prm->P))
+        tmp.get(&seg_start, ns) || tmp.get(&seg_end, ns) || tmp.get(&resv, (ns > 0 ? ns : 1) * (int64_t)prm->P))
         return -1;
     if (dalloc(&g->occ_start, ns, &g->device_bytes) || dalloc(&g->occ_kept, ns, &g->device_bytes) ||
         dalloc(&g->occ_routed, ns, &g->device_bytes) || dalloc(&g->occ_sc, ns, &g->device_bytes))
