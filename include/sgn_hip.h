@@ -320,6 +320,25 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
                         float *d_out_feat, float *d_out_blend, float *d_out_wnorm, void *d_workspace,
                         size_t workspace_bytes, sgn_stream_t stream);
 
+/* The viewmlp without block3 (shading_feature_mlp_layer3 = 0, point_aggregators.py:356-368, :638-653: block3 =
+ * passfunc; ABI 23, an addition) on the same plain-fp32 kernels.  Per row h = LReLU(block1.2(LReLU(block1.0(.)))),
+ * with bpnet_layers = 1 then h = LReLU(block2_bpnet.0([h | embedding])); alpha_k = softplus(alpha_branch.0(h) - 1);
+ * per sample alpha_s = sum_k w_k alpha_k, f_s = sum_k w_k h_k, colour = color_branch([f_s | PE(viewdir, 4)]).
+ * The arguments are those of the stock entries above, with these differences:
+ *   sgn_mlp_pack_exact_nb3  : the weights in the order block1.0, block1.2, alpha_branch.0, color_branch.0, .2,
+ *                             .4, .6 (+ block2_bpnet.0 as 7) -> blob of sgn_mlp_packed_bytes_exact_nb3 bytes
+ *   sgn_aggregate_exact_nb3 : pt->color and pt->dir are not read and may be NULL; every other check of
+ *                             sgn_aggregate_exact holds (K = 1 .. 8, alignment, workspace, rot with the base
+ *                             network only and without pers: the world half of dists and the colour MLP's view
+ *                             direction are rotated, there is no point direction to rotate) */
+size_t sgn_mlp_packed_bytes_exact_nb3(int32_t bpnet_layers, int32_t bpnet_dim);
+int sgn_mlp_pack_exact_nb3(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
+                           void *d_packed, sgn_stream_t stream);
+int sgn_aggregate_exact_nb3(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const sgn_point_tables *pt,
+                            const sgn_query_out *q, int64_t S_capacity, int32_t K, const void *d_packed_exact,
+                            float *d_out_feat, float *d_out_blend, float *d_out_wnorm, void *d_workspace,
+                            size_t workspace_bytes, sgn_stream_t stream);
+
 /* ---- training: forward with saved activations + backward ---
  * Gradients of PointAggregator.forward / viewmlp (point_aggregators.py:868-959, :561-786) and of
  * the NeuralPoints gather (neural_points.py:942-988) -- the reference gets them from torch autograd

@@ -9,7 +9,9 @@
 // with fp32 operands (each MFMA a k-ordered fmaf chain: exact fp32 products, fp32 sums) on the
 // weights exactly as the checkpoint holds them -- no power-of-two scaling, no fp16 anywhere, so
 // any activation fp32 holds is carried.  Slower than the split path (the fp32-input MFMA peak is
-// 1/16 of the fp16 one), and only used for frames the split path cannot represent.
+// 1/16 of the fp16 one), and only used for frames the split path cannot represent -- and for the
+// viewmlp without block3 (shading_feature_mlp_layer3 = 0, the B3 = false instantiations of the row
+// kernel; sgn_aggregate_exact_nb3), which the split kernels, ending in a transposed block3.2, cannot run.
 //
 // Layout: a wave owns 16 rows (2 samples x 8 neighbour slots; row k >= K or without a neighbour
 // is idle); lane l holds row r = l & 15 and, per output tile U of 16 units, units 16 U + 4 g + i
@@ -44,7 +46,9 @@ struct XLayout {
     uint32_t floats;
 };
 
-__host__ __device__ inline XLayout x_layout(int bpnet_layers, int bpnet_dim) {
+// block3_layers 0: the viewmlp without block3 (shading_feature_mlp_layer3 = 0, point_aggregators.py:356-368):
+// block3.0 / block3.2 take no space, as block2_bpnet.0 takes none in the base network
+__host__ __device__ inline XLayout x_layout(int bpnet_layers, int bpnet_dim, int block3_layers = 2) {
     XLayout x{};
     const int shape[NL][2] = {{284, 256}, {256, 256}, {256 + bpnet_dim, 256}, {263, 256}, {256, 256},
                               {256, 1},   {280, 128}, {128, 128},             {128, 128}, {128, 3}};
@@ -55,6 +59,7 @@ __host__ __device__ inline XLayout x_layout(int bpnet_layers, int bpnet_dim) {
         y.out = shape[L][1];
         y.in_pad = (y.in + 15) / 16 * 16;
         if (L == LBP && bpnet_layers == 0) y.in = y.in_pad = y.out = 0;
+        if ((L == LB30 || L == LB32) && block3_layers == 0) y.in = y.in_pad = y.out = 0;
         y.wt = off;
         off += (uint32_t)(y.in_pad * y.out);
         y.b = off;
@@ -118,6 +123,12 @@ __device__ __forceinline__ void layer_x(const float *__restrict__ wt, float *lds
     });
 }
 
+// a if C, else b (arrays of different extents)
+template <bool C, class A, class B>
+__device__ __forceinline__ auto &last_rows(A &a, B &b) {
+    if constexpr (C) return a; else return b;
+}
+
 template <int NU>
 __device__ __forceinline__ void bias_x(f32x4 (&acc)[NU], const float *b, int g) {
 #pragma unroll
@@ -132,7 +143,8 @@ struct XRow {
 };
 
 // ROT: rotated neural points (a.prot, a.samp_v; gather_row_impl states the three rules)
-template <bool PERS, bool ROT>
+// B3 false: no block3, so no ext[] -- a.color and a.dir are not read (they may be null)
+template <bool PERS, bool ROT, bool B3 = true>
 __device__ __forceinline__ XRow x_row(const AggArgs &a, const Cam &cam, int item, int end, int k) {
     XRow x;
     x.sval = item < end;
@@ -184,24 +196,29 @@ __device__ __forceinline__ XRow x_row(const AggArgs &a, const Cam &cam, int item
         if (a.blend) a.blend[s * a.K + k] = x.wgt;
         if (a.wnorm) a.wnorm[s * a.K + k] = w;
     }
-    // block3's extra channels: colour, dir - v, <dir, v> (:639-652)
-    const float c0 = a.color[pid * 3], c1 = a.color[pid * 3 + 1], c2 = a.color[pid * 3 + 2];
-    float e0 = a.dir[pid * 3], e1 = a.dir[pid * 3 + 1], e2 = a.dir[pid * 3 + 2];
-    if constexpr (ROT) rot3(R, e0, e1, e2, e0, e1, e2);
-    x.ext[0] = x.m ? c0 : 0.f;
-    x.ext[1] = x.m ? c1 : 0.f;
-    x.ext[2] = x.m ? c2 : 0.f;
-    x.ext[3] = x.m ? __fsub_rn(e0, vx) : 0.f;
-    x.ext[4] = x.m ? __fsub_rn(e1, vy) : 0.f;
-    x.ext[5] = x.m ? __fsub_rn(e2, vz) : 0.f;
-    x.ext[6] = x.m ? __fadd_rn(__fadd_rn(__fmul_rn(e0, vx), __fmul_rn(e1, vy)), __fmul_rn(e2, vz)) : 0.f;
-    x.ext[7] = 0.f;
+    if constexpr (B3) {
+        // block3's extra channels: colour, dir - v, <dir, v> (:639-652)
+        const float c0 = a.color[pid * 3], c1 = a.color[pid * 3 + 1], c2 = a.color[pid * 3 + 2];
+        float e0 = a.dir[pid * 3], e1 = a.dir[pid * 3 + 1], e2 = a.dir[pid * 3 + 2];
+        if constexpr (ROT) rot3(R, e0, e1, e2, e0, e1, e2);
+        x.ext[0] = x.m ? c0 : 0.f;
+        x.ext[1] = x.m ? c1 : 0.f;
+        x.ext[2] = x.m ? c2 : 0.f;
+        x.ext[3] = x.m ? __fsub_rn(e0, vx) : 0.f;
+        x.ext[4] = x.m ? __fsub_rn(e1, vy) : 0.f;
+        x.ext[5] = x.m ? __fsub_rn(e2, vz) : 0.f;
+        x.ext[6] = x.m ? __fadd_rn(__fadd_rn(__fmul_rn(e0, vx), __fmul_rn(e1, vy)), __fmul_rn(e2, vz)) : 0.f;
+        x.ext[7] = 0.f;
+    }
     return x;
 }
 
 // SG: KSG > 0 adds block2_bpnet.0 ([h | BPNet embedding of bpnet_dim] -> 256) between block1.2
 // and block3.0 (point_aggregators.py:345-354, :629-636)
-template <bool PERS, int NTB, bool ROT = false>
+// B3 false: the viewmlp without block3 (self.block3 = passfunc, :356-368): block3.0 / block3.2 are not
+// instantiated and the epilogue takes the array block1.2 / block2_bpnet.0 left (compile-time: layer_x holds
+// workgroup barriers)
+template <bool PERS, int NTB, bool ROT = false, bool B3 = true>
 __global__ __launch_bounds__(TPB, 1) void k_rows_exact(XArgs xa) {
     __shared__ __attribute__((aligned(16))) float lds[KCH * LSTR];
     const AggArgs &a = xa.a;
@@ -217,7 +234,7 @@ __global__ __launch_bounds__(TPB, 1) void k_rows_exact(XArgs xa) {
         int g = lane >> 4;
         asm volatile("" : "+v"(g));
         const int item = a.item0 + tile * 2 * NW + 2 * w + (r >> 3);
-        const XRow x = x_row<PERS, ROT>(a, cam, item, end, k);
+        const XRow x = x_row<PERS, ROT, B3>(a, cam, item, end, k);
         const int64_t pid = x.m ? x.pid : 0;
         const float *emb = a.emb + pid * 32;
         // block1.0: [feat 32 | PE(feat, 3) 192 | PE(dists, 5) 60] (networks.py:175-192: sin / cos
@@ -283,24 +300,27 @@ __global__ __launch_bounds__(TPB, 1) void k_rows_exact(XArgs xa) {
         }
         auto &hin = pick<(NTB > 0)>(h0, h1);
         // block3.0: [h 256 | colour, dir - v, <dir, v>] -> 256, into the array block1.2 / block2_bpnet left
-        f32x4 h2[16];
-        bias_x(h2, xa.w + ly.l[LB30].b, g);
-        layer_x<16, 17>(xa.w + ly.l[LB30].wt, lds, h2, g, r, [&](auto tc) {
-            constexpr int T = decltype(tc)::value;
-            f32x4 v;
-            if constexpr (T < 16) {
+        f32x4 h2[B3 ? 16 : 1], h3s[B3 ? 16 : 1];
+        if constexpr (B3) {
+            bias_x(h2, xa.w + ly.l[LB30].b, g);
+            layer_x<16, 17>(xa.w + ly.l[LB30].wt, lds, h2, g, r, [&](auto tc) {
+                constexpr int T = decltype(tc)::value;
+                f32x4 v;
+                if constexpr (T < 16) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = lrelu_x(hin[T][i]);
-            } else {
+                    for (int i = 0; i < 4; ++i) v[i] = lrelu_x(hin[T][i]);
+                } else {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = g == 0 ? x.ext[i] : g == 1 ? x.ext[4 + i] : 0.f;
-            }
-            return v;
-        });
-        f32x4 h3[16];
-        bias_x(h3, xa.w + ly.l[LB32].b, g);
-        layer_x<16, 16>(xa.w + ly.l[LB32].wt, lds, h3, g, r, chain(h2));
-        // epilogue (:743-770): h = LReLU(block3.2), alpha = softplus(W_a h + b_a - 1), K-blend of
+                    for (int i = 0; i < 4; ++i) v[i] = g == 0 ? x.ext[i] : g == 1 ? x.ext[4 + i] : 0.f;
+                }
+                return v;
+            });
+            bias_x(h3s, xa.w + ly.l[LB32].b, g);
+            layer_x<16, 16>(xa.w + ly.l[LB32].wt, lds, h3s, g, r, chain(h2));
+        }
+        // the last row layer's pre-activations: block3.2's, or without block3 those of block1.2 / block2_bpnet.0
+        f32x4(&h3)[16] = last_rows<B3>(h3s, hin);
+        // epilogue (:743-770): h = LReLU(last row layer), alpha = softplus(W_a h + b_a - 1), K-blend of
         // h and alpha over the sample's rows with weight * conf
         const float *wa = xa.w + ly.l[LA].wt;
         float dot = 0.f;
@@ -421,16 +441,23 @@ size_t sgn_mlp_packed_bytes_exact(int32_t bpnet_layers, int32_t bpnet_dim) {
     return (size_t)sgn::xe::x_layout(bpnet_layers, bpnet_dim).floats * 4;
 }
 
+size_t sgn_mlp_packed_bytes_exact_nb3(int32_t bpnet_layers, int32_t bpnet_dim) {
+    if (sgn::mlp::variant_ksb(bpnet_layers, bpnet_dim) < 0) return 0;
+    return (size_t)sgn::xe::x_layout(bpnet_layers, bpnet_dim, 0).floats * 4;
+}
+
 // weights in the order of sgn_mlp_pack_f32: block1.0, block1.2, block3.0, block3.2, alpha_branch.0,
 // color_branch.0, .2, .4, .6 (+ block2_bpnet.0 as 9); W [out][in] row-major fp32 as nn.Linear holds it
-int sgn_mlp_pack_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
-                       void *d_packed, sgn_stream_t stream) {
+static int pack_exact(int32_t bpnet_layers, int32_t bpnet_dim, int block3_layers, const float *const *w,
+                      const float *const *b, void *d_packed, sgn_stream_t stream) {
     using namespace sgn;
     using namespace sgn::xe;
     SGN_REQUIRE(w && b && d_packed, "null argument");
     SGN_REQUIRE_VARIANT(variant_ksb(bpnet_layers, bpnet_dim));
-    const XLayout ly = x_layout(bpnet_layers, bpnet_dim);
-    const int src[NL] = {0, 1, 9, 2, 3, 4, 5, 6, 7, 8};  // x_layout layer -> argument index
+    const XLayout ly = x_layout(bpnet_layers, bpnet_dim, block3_layers);
+    // x_layout layer -> argument index (without block3: block1.0, block1.2, alpha, colour 0 .. 6, block2_bpnet.0)
+    const int src3[NL] = {0, 1, 9, 2, 3, 4, 5, 6, 7, 8}, src0[NL] = {0, 1, 7, -1, -1, 2, 3, 4, 5, 6};
+    const int *src = block3_layers ? src3 : src0;
     std::vector<float> blob(ly.floats, 0.f);
     for (int L = 0; L < NL; ++L) {
         const XLayer &y = ly.l[L];
@@ -452,10 +479,26 @@ int sgn_mlp_pack_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *con
     return 0;
 }
 
-int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const sgn_point_tables *pt,
-                        const sgn_query_out *q, int64_t S_capacity, int32_t K, const void *d_packed_exact,
-                        float *d_out_feat, float *d_out_blend, float *d_out_wnorm, void *d_workspace,
-                        size_t workspace_bytes, sgn_stream_t stream) {
+int sgn_mlp_pack_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
+                       void *d_packed, sgn_stream_t stream) {
+    return pack_exact(bpnet_layers, bpnet_dim, 2, w, b, d_packed, stream);
+}
+
+// the viewmlp without block3: weights in the order block1.0, block1.2, alpha_branch.0, color_branch.0, .2, .4,
+// .6 (+ block2_bpnet.0 as 7)
+int sgn_mlp_pack_exact_nb3(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
+                           void *d_packed, sgn_stream_t stream) {
+    return pack_exact(bpnet_layers, bpnet_dim, 0, w, b, d_packed, stream);
+}
+
+}  // extern "C"
+
+// B3: the stock network, or (false) the viewmlp without block3, which reads neither pt->color nor pt->dir
+template <bool B3>
+static int aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const sgn_point_tables *pt,
+                           const sgn_query_out *q, int64_t S_capacity, int32_t K, const void *d_packed_exact,
+                           float *d_out_feat, float *d_out_blend, float *d_out_wnorm, void *d_workspace,
+                           size_t workspace_bytes, sgn_stream_t stream) {
     using namespace sgn;
     using namespace sgn::xe;
     SGN_REQUIRE(pt && q && d_packed_exact && d_out_feat && d_workspace, "null argument");
@@ -463,7 +506,7 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
     SGN_REQUIRE(bpnet_dim == 0 || (d_bpnet && ((uintptr_t)d_bpnet & 15) == 0),
                 "bpnet_dim > 0 needs the 16-byte aligned fp32 BPNet point embedding");
     SGN_REQUIRE(K >= 1 && K <= 8, "the aggregator takes K = 1 .. 8 neighbours per sample");
-    SGN_REQUIRE(pt->xyz && pt->embedding && pt->color && pt->dir && pt->conf, "point tables required");
+    SGN_REQUIRE(pt->xyz && pt->embedding && pt->conf && (!B3 || (pt->color && pt->dir)), "point tables required");
     SGN_REQUIRE(((uintptr_t)pt->embedding & 15) == 0 && ((uintptr_t)d_packed_exact & 15) == 0 &&
                     ((uintptr_t)d_workspace & 15) == 0,
                 "16-byte alignment required");
@@ -482,7 +525,7 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
     a.bpnet32 = d_bpnet;
     a.feat = d_out_feat; a.blend = d_out_blend; a.wnorm = d_out_wnorm;
     x.w = (const float *)d_packed_exact;
-    x.lay = x_layout(bpnet_layers, bpnet_dim);
+    x.lay = x_layout(bpnet_layers, bpnet_dim, B3 ? 2 : 0);
     x.fs = (float *)d_workspace;
     x.bpnet_dim = bpnet_dim;
     const int ntb = bpnet_layers ? (256 + bpnet_dim) / 16 : 0;
@@ -495,20 +538,38 @@ int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_
         const int64_t tr = (a.n_items + 2 * NW - 1) / (2 * NW), tc = (a.n_items + 16 * NW - 1) / (16 * NW);
         const dim3 gr((unsigned)(tr < 2048 ? tr : 2048)), gc((unsigned)(tc < 1024 ? tc : 1024));
         if (pt->rot) {  // base network, no pers (SGN_REQUIRE_ROT)
-            hipLaunchKernelGGL((k_rows_exact<false, 0, true>), gr, dim3(TPB), 0, st, x);
+            hipLaunchKernelGGL((k_rows_exact<false, 0, true, B3>), gr, dim3(TPB), 0, st, x);
         } else if (pt->pers) {
-            if (ntb == 0) hipLaunchKernelGGL((k_rows_exact<true, 0>), gr, dim3(TPB), 0, st, x);
-            else if (ntb == 16) hipLaunchKernelGGL((k_rows_exact<true, 16>), gr, dim3(TPB), 0, st, x);
-            else hipLaunchKernelGGL((k_rows_exact<true, 22>), gr, dim3(TPB), 0, st, x);
+            if (ntb == 0) hipLaunchKernelGGL((k_rows_exact<true, 0, false, B3>), gr, dim3(TPB), 0, st, x);
+            else if (ntb == 16) hipLaunchKernelGGL((k_rows_exact<true, 16, false, B3>), gr, dim3(TPB), 0, st, x);
+            else hipLaunchKernelGGL((k_rows_exact<true, 22, false, B3>), gr, dim3(TPB), 0, st, x);
         } else {
-            if (ntb == 0) hipLaunchKernelGGL((k_rows_exact<false, 0>), gr, dim3(TPB), 0, st, x);
-            else if (ntb == 16) hipLaunchKernelGGL((k_rows_exact<false, 16>), gr, dim3(TPB), 0, st, x);
-            else hipLaunchKernelGGL((k_rows_exact<false, 22>), gr, dim3(TPB), 0, st, x);
+            if (ntb == 0) hipLaunchKernelGGL((k_rows_exact<false, 0, false, B3>), gr, dim3(TPB), 0, st, x);
+            else if (ntb == 16) hipLaunchKernelGGL((k_rows_exact<false, 16, false, B3>), gr, dim3(TPB), 0, st, x);
+            else hipLaunchKernelGGL((k_rows_exact<false, 22, false, B3>), gr, dim3(TPB), 0, st, x);
         }
         hipLaunchKernelGGL(pt->rot ? k_color_exact<true> : k_color_exact<false>, gc, dim3(TPB), 0, st, x);
     }
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" {
+
+int sgn_aggregate_exact(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const sgn_point_tables *pt,
+                        const sgn_query_out *q, int64_t S_capacity, int32_t K, const void *d_packed_exact,
+                        float *d_out_feat, float *d_out_blend, float *d_out_wnorm, void *d_workspace,
+                        size_t workspace_bytes, sgn_stream_t stream) {
+    return aggregate_exact<true>(bpnet_layers, bpnet_dim, d_bpnet, pt, q, S_capacity, K, d_packed_exact, d_out_feat,
+                                 d_out_blend, d_out_wnorm, d_workspace, workspace_bytes, stream);
+}
+
+int sgn_aggregate_exact_nb3(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const sgn_point_tables *pt,
+                            const sgn_query_out *q, int64_t S_capacity, int32_t K, const void *d_packed_exact,
+                            float *d_out_feat, float *d_out_blend, float *d_out_wnorm, void *d_workspace,
+                            size_t workspace_bytes, sgn_stream_t stream) {
+    return aggregate_exact<false>(bpnet_layers, bpnet_dim, d_bpnet, pt, q, S_capacity, K, d_packed_exact, d_out_feat,
+                                  d_out_blend, d_out_wnorm, d_workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

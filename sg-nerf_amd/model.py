@@ -39,7 +39,7 @@ import torch
 from .opts import HotPathOpts
 from .ray_marching import NeuralPoints, NeuralPointsRayMarching
 from .train import depth_target
-from .weights import strip_prefix
+from .weights import block3_layers, strip_prefix
 
 LOSS_NAMES = ["total", "ray_masked_coarse_raycolor", "ray_miss_coarse_raycolor", "coarse_raycolor",
               "conf_coefficient"]
@@ -164,7 +164,7 @@ class HipPointsVolumetricModel:
             if 0.0 < dc <= 1.0:
                 points_conf = torch.ones_like(torch.as_tensor(points_conf), dtype=torch.float32) * dc
         for name, t in (("points_color", points_color), ("points_dir", points_dir)):
-            if t is None:
+            if t is None and self.opts.block3_layers:   # without block3 neither is read
                 raise NotImplementedError(f"set_points without {name}: the MFMA aggregator's inputs include it")
         self.neural_points = NeuralPoints(points_xyz, points_embedding, points_color, points_dir, points_conf,
                                           self.device, points_feats=points_feats, points_label=points_label,
@@ -183,6 +183,12 @@ class HipPointsVolumetricModel:
             self.optimizers = []
         elif self.is_train:
             self.setup_optimizer(self.opt)
+
+    def _check_trainable(self):
+        """The viewmlp without block3 renders only (the plain-fp32 kernels have no backward)."""
+        if not self.opts.block3_layers:
+            raise NotImplementedError("shading_feature_mlp_layer3 = 0 renders only: training this network is not "
+                                      "implemented (it runs on the plain-fp32 kernels, which have no backward)")
 
     def _check_rotation(self, training=False):
         """What a non-identity Rw2c does not combine with: the SG variant (block2_bpnet) and training."""
@@ -205,6 +211,7 @@ class HipPointsVolumetricModel:
         trainer's tensors either way."""
         from .train import PointParams
         from .train_hip import HipTrainer
+        self._check_trainable()
         if self.neural_points is None or self.net_ray_marching is None:
             raise RuntimeError("setup_optimizer: no neural points / aggregator weights yet")
         self._check_rotation(training=True)
@@ -369,6 +376,7 @@ class HipPointsVolumetricModel:
 
     def optimize_parameters(self, backward=True, total_steps=0):
         """neural_points_volumetric_model.py:320-331: forward, losses, backward, both Adam steps."""
+        self._check_trainable()
         self._check_rotation(training=True)
         w_d = self.opts.depth_loss_weight
         if w_d is not None and self.input.get("gt_depth") is None:
@@ -531,8 +539,12 @@ class HipPointsVolumetricModel:
         directory = directory or getattr(self.opt, "resume_dir", None) or self.save_dir
         path = os.path.join(directory, f"{epoch}_net_ray_marching.pth")
         sd = torch.load(path, map_location="cpu", weights_only=True)
+        if block3_layers(sd) != self.opts.block3_layers:
+            raise ValueError(f"{path} holds {block3_layers(sd)} block3 layers, the options say "
+                             f"shading_feature_mlp_layer3 = {self.opts.block3_layers}")
         self.neural_points = NeuralPoints.from_state_dict(sd, self.device)
         self._check_rotation()
-        self.net_ray_marching = NeuralPointsRayMarching(self.neural_points, strip_prefix(sd), self.opts, self.device,
-                                                        return_weights=self._return_weights)
+        self.net_ray_marching = NeuralPointsRayMarching(self.neural_points,
+                                                        strip_prefix(sd, block3_layers=block3_layers(sd)), self.opts,
+                                                        self.device, return_weights=self._return_weights)
         return path

@@ -120,6 +120,12 @@ class HotPathOpts:
         return 1, (96 if self.predict_semantic == 1 else 0)
 
     @property
+    def block3_layers(self):
+        """block3's layer count: 2, or 0 for the viewmlp without block3 (point_aggregators.py:356-368), which
+        the plain-fp32 kernels render (sgn_aggregate_exact_nb3)."""
+        return int(self.shading_feature_mlp_layer3)
+
+    @property
     def trained_points(self):
         """The trained point tensors' names, in the point Adam group's order."""
         sw = (("points_embeding", self.feat_grad), ("points_color", self.color_grad), ("points_dir", self.dir_grad),
@@ -236,8 +242,14 @@ class HotPathOpts:
                 self.num_viewdir_freqs) != (32, 256, 3, 5, 4):
             bad.append("MLP widths/frequencies must match the ScanNet viewmlp (32/256/3/5/4)")
         if (self.shading_feature_mlp_layer1, self.shading_feature_mlp_layer2, self.shading_feature_mlp_layer3,
-                self.shading_alpha_mlp_layer, self.shading_color_mlp_layer) != (2, 0, 2, 1, 4):
-            bad.append("viewmlp layer counts must be (2, 0, 2, 1, 4)")
+                self.shading_alpha_mlp_layer, self.shading_color_mlp_layer) not in ((2, 0, 2, 1, 4), (2, 0, 0, 1, 4)):
+            bad.append("viewmlp layer counts must be (2, 0, 2, 1, 4), or (2, 0, 0, 1, 4) without block3")
+        elif self.shading_feature_mlp_layer3 == 0:
+            # the viewmlp without block3 (point_aggregators.py:356-368) renders on the plain-fp32 kernels only
+            if self.precision == "f16":
+                bad.append("shading_feature_mlp_layer3 = 0 is rendered in plain fp32 only: precision must be 'f32', not 'f16'")
+            if self.is_train:
+                bad.append("shading_feature_mlp_layer3 = 0 renders only: training (is_train) is not implemented")
         if self.shading_feature_mlp_layer2_bpnet not in (0, 1):
             bad.append("block2_bpnet: at most one layer (shading_feature_mlp_layer2_bpnet 0 or 1)")
         elif self.shading_feature_mlp_layer2_bpnet == 1 and bool(self.predict_semantic) != bool(self.semantic_guidance):

@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from .opts import HotPathOpts
 from .render import HipRenderer, PointTables
-from .weights import mlp_variant, pack_mlp, strip_prefix
+from .weights import block3_layers, mlp_variant, pack_mlp, strip_prefix
 
 
 def _bg_tuple(bg_color, opts):
@@ -68,8 +68,9 @@ class NeuralPoints:
         self.xyz = torch.as_tensor(xyz).to(**f).reshape(-1, 3)
         n = self.xyz.shape[0]
         self.points_embeding = torch.as_tensor(points_embeding).to(**f).reshape(1, n, -1)
-        self.points_color = torch.as_tensor(points_color).to(**f).reshape(1, n, 3)
-        self.points_dir = torch.as_tensor(points_dir).to(**f).reshape(1, n, 3)
+        # None: the viewmlp without block3 (shading_feature_mlp_layer3 = 0) reads neither
+        self.points_color = None if points_color is None else torch.as_tensor(points_color).to(**f).reshape(1, n, 3)
+        self.points_dir = None if points_dir is None else torch.as_tensor(points_dir).to(**f).reshape(1, n, 3)
         self.points_conf = torch.as_tensor(points_conf).to(**f).reshape(1, n, 1)
         self.Rw2c = torch.eye(3, **f) if Rw2c is None else self._check_Rw2c(Rw2c, n, dev)
         self.device = dev
@@ -112,7 +113,7 @@ class NeuralPoints:
         two are optional here as they are there)."""
         g = lambda k: sd[prefix + k]  # noqa: E731
         o = lambda k: sd.get(prefix + k)  # noqa: E731
-        p = cls(g("xyz"), g("points_embeding"), g("points_color"), g("points_dir"), g("points_conf"), device,
+        p = cls(g("xyz"), g("points_embeding"), o("points_color"), o("points_dir"), g("points_conf"), device,
                 points_feats=o("points_feats"), points_label=o("points_label"),
                 bpnet_points_embedding=o("bpnet_points_embedding"))
         if o("Rw2c") is not None:
@@ -127,14 +128,16 @@ class NeuralPoints:
         """The reference's keys; the semantic ones only when set (a reference loader reads
         points_feats unconditionally, so checkpoints meant for it need set_points(points_feats=...))."""
         sd = {prefix + k: getattr(self, k) for k in
-              ("xyz", "points_embeding", "points_color", "points_dir", "points_conf", "Rw2c")}
+              ("xyz", "points_embeding", "points_color", "points_dir", "points_conf", "Rw2c")
+              if getattr(self, k) is not None}
         for k in ("points_feats", "points_label", "bpnet_points_embedding"):
             if getattr(self, k) is not None:
                 sd[prefix + k] = getattr(self, k)
         return sd
 
     def _version_key(self):
-        ts = (self.xyz, self.points_embeding, self.points_color, self.points_dir, self.points_conf, self.Rw2c)
+        ts = tuple(t for t in (self.xyz, self.points_embeding, self.points_color, self.points_dir, self.points_conf,
+                               self.Rw2c) if t is not None)
         if self.bpnet_points_embedding is not None:
             ts = ts + (self.bpnet_points_embedding,)
         return tuple((t.data_ptr(), tuple(t.shape), t._version) for t in ts)
@@ -258,10 +261,13 @@ class NeuralPointsRayMarching:
         self.neural_points = neural_points
         self.device = torch.device(device)
         self.return_weights = return_weights
-        self.renderer = HipRenderer(neural_points.tables(), strip_prefix(aggregator_state), self.opts, self.device)
+        self.renderer = HipRenderer(neural_points.tables(), self._strip(aggregator_state), self.opts, self.device)
+
+    def _strip(self, state):
+        return strip_prefix(state, block3_layers=block3_layers(state))
 
     def set_aggregator_state(self, state):
-        self.renderer.set_mlp(strip_prefix(state))
+        self.renderer.set_mlp(self._strip(state))
 
     def _prob(self, prob):
         if prob is None:
@@ -364,13 +370,22 @@ class PointAggregator:
         self.opts = opt if isinstance(opt, HotPathOpts) else (HotPathOpts.from_opt(opt) if opt is not None
                                                                else HotPathOpts())
         self.device = torch.device(device)
-        state = strip_prefix(aggregator_state)
+        self.block3 = block3_layers(aggregator_state)
+        if self.block3 != self.opts.block3_layers:
+            raise ValueError(f"aggregator weights hold {self.block3} block3 layers, options say "
+                             f"shading_feature_mlp_layer3 = {self.opts.block3_layers}")
+        state = strip_prefix(aggregator_state, block3_layers=self.block3)
         self.variant = mlp_variant(state)
         # fp32 arithmetic (the reference's) unless opts say f16
         self.f32 = self.opts.precision == "f32"
-        self.packed = pack_mlp(state, self.device, self.opts.precision)
         self.state = state              # fp32 weights for the range fallback's plain-fp32 pack
         self.packed_exact = None
+        if not self.block3:   # the viewmlp without block3: the plain-fp32 kernels only (sgn_aggregate_exact_nb3)
+            self.opts.check_supported()
+            self.packed = None
+            self.packed_exact = pack_mlp(state, self.device, "exact", block3_layers=0)
+            return
+        self.packed = pack_mlp(state, self.device, self.opts.precision)
 
     def forward(self, sampled_color, sampled_label_embedding, sampled_Rw2c, sampled_dir, sampled_conf,
                 sampled_embedding, sampled_xyz_pers, sampled_xyz, sample_pnt_mask, sample_loc, sample_loc_w,
@@ -394,7 +409,7 @@ class PointAggregator:
         rows = torch.arange(S * K, device=dev, dtype=torch.int32).view(S, K)
         pidx = torch.where(mask, rows, torch.full_like(rows, -1))
         order = None
-        if self.f32:
+        if self.f32 and self.block3:
             # the f32 row kernel reads a sample's valid neighbours as a prefix of its K slots (as the
             # query writes them); a caller's mask may have holes: move each sample's valid slots to
             # the front (stable, so the K-blend sums them in the reference's slot order; the empty
@@ -411,14 +426,20 @@ class PointAggregator:
         samp_ray = torch.arange(S, device=dev, dtype=torch.int32)
         xyz, pers = f(sampled_xyz, 3), f(sampled_xyz_pers, 3)
         emb = f(sampled_embedding, 32)
-        col, pdir, conf = f(sampled_color, 3), f(sampled_dir, 3), f(sampled_conf, 1)
+        if self.block3 and (sampled_color is None or sampled_dir is None):
+            raise ValueError("PointAggregator.forward: block3 reads sampled_color and sampled_dir")
+        # without block3 neither is read (point_aggregators.py:638-653)
+        col = f(sampled_color, 3) if self.block3 else None
+        pdir = f(sampled_dir, 3) if self.block3 else None
+        conf = f(sampled_conf, 1)
         locw, loc = f(sample_loc_w, 3), f(sample_loc, 3)
         vdir = f(sample_ray_dirs, 3)
         zero3 = torch.zeros(3, device=dev)
         eye = torch.eye(3, device=dev)
         pt = _lib.PointTables()
-        pt.xyz, pt.embedding, pt.color = xyz.data_ptr(), emb.data_ptr(), col.data_ptr()
-        pt.dir, pt.conf, pt.n_points = pdir.data_ptr(), conf.data_ptr(), S * K
+        pt.xyz, pt.embedding, pt.conf, pt.n_points = xyz.data_ptr(), emb.data_ptr(), conf.data_ptr(), S * K
+        if self.block3:
+            pt.color, pt.dir = col.data_ptr(), pdir.data_ptr()
         pt.campos, pt.camrotc2w, pt.raydir = zero3.data_ptr(), eye.data_ptr(), vdir.data_ptr()
         pt.pers, pt.samp_pers = pers.data_ptr(), loc.data_ptr()
         nl, dim = self.variant
@@ -427,7 +448,7 @@ class PointAggregator:
             if sampled_label_embedding is None:
                 raise ValueError("block2_bpnet with predict_semantic = 1 needs sampled_label_embedding")
             lab = f(sampled_label_embedding, 96)
-            if self.f32:
+            if self.f32 or not self.block3:
                 bp = lab
             else:
                 bp = torch.empty(S * K, 96, dtype=torch.float16, device=dev)
@@ -441,7 +462,14 @@ class PointAggregator:
         wnorm = torch.zeros(S, K, dtype=torch.float32, device=dev)
         L = _lib.lib()
         st = _lib.stream_handle()
-        if self.f32:
+        if not self.block3:
+            # the viewmlp without block3: plain fp32, no projection; the kernel takes a caller's mask with holes as
+            # it is (every slot is a row of its own), so the slot order stays the caller's
+            ws = torch.empty(max(S, 1) * 1024, dtype=torch.uint8, device=dev)
+            _lib.check(L.sgn_aggregate_exact_nb3(nl, dim, _lib.ptr(bp), ctypes.byref(pt), ctypes.byref(qo), S, K,
+                                                 _lib.ptr(self.packed_exact), _lib.ptr(feat), None, _lib.ptr(wnorm),
+                                                 _lib.ptr(ws), ws.numel(), st), "sgn_aggregate_exact_nb3")
+        elif self.f32:
             # block1.0's per-point part over the gathered rows (each row is its own "point")
             proj = torch.empty(int(L.sgn_point_proj_bytes_f32(S * K)), dtype=torch.uint8, device=dev)
             _lib.check(L.sgn_point_project_f32(ctypes.byref(pt), _lib.ptr(self.packed), None, None, _lib.ptr(proj), st),

@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from .opts import HotPathOpts
 from .querier import LightningFastQuerier
-from .weights import mlp_variant, pack_mlp, strip_prefix
+from .weights import block3_layers, mlp_variant, pack_mlp, strip_prefix
 
 
 @dataclass
@@ -39,7 +39,10 @@ class PointTables:
 
     `rot`: the reference's Rw2c (neural_points.py:967), [N,3,3] per point or one [3,3] for every
     point -> the [N,9] table the rotated kernels read.  A table that is exactly identity is kept as
-    None: such clouds run the stock kernels, bit for bit."""
+    None: such clouds run the stock kernels, bit for bit.
+
+    `color` / `dir` may be None for the viewmlp without block3 (shading_feature_mlp_layer3 = 0), which reads
+    neither; every other consumer (the stock aggregators, the hole probe) refuses such tables."""
 
     def __init__(self, xyz, embedding, color, dir, conf, device, bpnet=None, rot=None):
         def t(x, cols):
@@ -47,8 +50,8 @@ class PointTables:
             return x.to(device=device, dtype=torch.float32).contiguous()
         self.xyz = t(xyz, 3)
         self.embedding = t(embedding, 32)
-        self.color = t(color, 3)
-        self.dir = t(dir, 3)
+        self.color = None if color is None else t(color, 3)
+        self.dir = None if dir is None else t(dir, 3)
         self.conf = t(conf, 1)
         self.n = self.xyz.shape[0]
         self.bpnet16 = None
@@ -104,13 +107,25 @@ class HipRenderer:
         self._tiered = False   # the last frame was aggregated tier by tier (early ray termination)
 
     def set_mlp(self, mlp_state):
+        nb3 = block3_layers(mlp_state)
+        if nb3 != self.opts.block3_layers:
+            raise ValueError(f"aggregator weights hold {nb3} block3 layers, options say "
+                             f"shading_feature_mlp_layer3 = {self.opts.block3_layers}")
+        self.block3 = nb3
         self.mlp_state = {k: torch.as_tensor(v).detach().to("cpu", torch.float32)
-                          for k, v in strip_prefix(mlp_state).items()}
+                          for k, v in strip_prefix(mlp_state, block3_layers=nb3).items()}
         self.variant = mlp_variant(self.mlp_state)
         if self.variant != self.opts.bpnet_variant:
             raise ValueError(f"aggregator weights are block2_bpnet variant {self.variant}, options say "
                              f"{self.opts.bpnet_variant} (shading_feature_mlp_layer2_bpnet / predict_semantic)")
         self.f32 = self.opts.precision == "f32"
+        if not self.block3:
+            # the viewmlp without block3 lives on the plain-fp32 path only (sgn_aggregate_exact_nb3): no split-fp16
+            # blob, no point projection, no fp16-range check, and (as on that path, _tiers) no early-stop tiers
+            self.packed = None
+            self.packed_exact = pack_mlp(self.mlp_state, self.device, "exact", block3_layers=0)
+            self.exact = True
+            return
         self.packed = pack_mlp(self.mlp_state, self.device, self.opts.precision)
         # f32 mode's range fallback: plain fp32 weights for sgn_aggregate_exact, packed on first use; `exact`
         # turns on (for these weights) once a frame's activations left fp16 range
@@ -266,8 +281,15 @@ class HipRenderer:
         L = _lib.lib()
         st = _lib.stream_handle()
         pt = _lib.PointTables()
-        pt.xyz, pt.embedding, pt.color = self.points.xyz.data_ptr(), self.points.embedding.data_ptr(), self.points.color.data_ptr()
-        pt.dir, pt.conf, pt.n_points = self.points.dir.data_ptr(), self.points.conf.data_ptr(), self.points.n
+        pts = self.points
+        if self.block3 and (pts.color is None or pts.dir is None):
+            raise ValueError("point tables without colour / dir: block3 reads both (only the viewmlp without block3, "
+                             "shading_feature_mlp_layer3 = 0, renders without them)")
+        if want_probe and (pts.color is None or pts.dir is None):
+            raise ValueError("the hole probe (want_probe) averages the points' colour and dir: the point tables hold none")
+        pt.xyz, pt.embedding, pt.conf, pt.n_points = pts.xyz.data_ptr(), pts.embedding.data_ptr(), pts.conf.data_ptr(), pts.n
+        pt.color = None if pts.color is None else pts.color.data_ptr()
+        pt.dir = None if pts.dir is None else pts.dir.data_ptr()
         pt.campos, pt.camrotc2w, pt.raydir = campos.data_ptr(), rot.data_ptr(), raydir.data_ptr()
         qo = q.abi()
         cap = R * o.SR
@@ -287,17 +309,20 @@ class HipRenderer:
             # the f32 mode's range fallback: the whole aggregator and colour MLP in plain fp32
             if self.packed_exact is None:
                 self.packed_exact = pack_mlp(self.mlp_state, self.device, "exact")
-            _lib.check(L.sgn_aggregate_exact(nl, dim, bp, ctypes.byref(pt), ctypes.byref(qo), cap, o.K,
-                                             _lib.ptr(self.packed_exact), _lib.ptr(self.feat),
-                                             _lib.ptr(self.blend) if want_blend else None,
-                                             _lib.ptr(self.wnorm) if want_weights else None, _lib.ptr(self.agg_ws),
-                                             self.agg_ws.numel(), _lib.stream_handle()), "sgn_aggregate_exact")
+            entry, name = ((L.sgn_aggregate_exact, "sgn_aggregate_exact") if self.block3 else
+                           (L.sgn_aggregate_exact_nb3, "sgn_aggregate_exact_nb3"))
+            _lib.check(entry(nl, dim, bp, ctypes.byref(pt), ctypes.byref(qo), cap, o.K,
+                             _lib.ptr(self.packed_exact), _lib.ptr(self.feat),
+                             _lib.ptr(self.blend) if want_blend else None,
+                             _lib.ptr(self.wnorm) if want_weights else None, _lib.ptr(self.agg_ws),
+                             self.agg_ws.numel(), _lib.stream_handle()), name)
 
         # split block1.0: P[point] = W0a [feat | PE(feat)] + b0, once per frame, for the points the
         # frame's samples name only (sgn_frame_points: ~19 % of a config-2 frame's)
         mark("proj")
-        nproj = int(L.sgn_point_proj_bytes_f32(self.points.n) if self.f32 else L.sgn_point_proj_bytes(self.points.n))
-        if self._proj is None or self._proj.numel() < nproj:
+        nproj = 0 if not self.block3 else int(L.sgn_point_proj_bytes_f32(self.points.n) if self.f32 else
+                                              L.sgn_point_proj_bytes(self.points.n))
+        if self.block3 and (self._proj is None or self._proj.numel() < nproj):
             self._proj = torch.empty(max(nproj, 16), dtype=torch.uint8, device=self.device)
         if not self.exact:
             n = self.points.n

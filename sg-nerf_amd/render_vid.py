@@ -30,11 +30,11 @@ def spiral_views(n_frames, h, w, campos=(2.0, 2.0, 1.5)):
     return out
 
 
-def default_scene(n_points=1_200_000):
+def default_scene(n_points=1_200_000, block3_layers=2):
     """Config 3's synthetic stand-in: synth-room cloud and a random aggregator whose alpha
     bias (+50) makes the volume opaque (median background transmission ~0.4 at SR 24)."""
     pc = scene.synth_room(n_points, seed=0)
-    mlp = init_mlp(0, bias_std=0.01)
+    mlp = init_mlp(0, bias_std=0.01, block3_layers=block3_layers)
     mlp["alpha_branch.0.bias"] = mlp["alpha_branch.0.bias"] + 50.0
     return pc, mlp
 
@@ -79,6 +79,9 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--precision", default="f32", choices=["f32", "f16"])
     ap.add_argument("--early_stop", type=float, default=0.0, help="early ray termination threshold (0 = off)")
+    ap.add_argument("--mlp_layer3", type=int, default=2, choices=[0, 2],
+                    help="shading_feature_mlp_layer3: 0 = the viewmlp without block3 (the SG-NeRF scripts' network; "
+                         "plain fp32, --precision f32 only)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -87,15 +90,16 @@ def main(argv=None):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group("nccl", device_id=dev)
-    o = HotPathOpts(SR=args.sr, precision=args.precision, early_stop=args.early_stop)
+    o = HotPathOpts(SR=args.sr, precision=args.precision, early_stop=args.early_stop,
+                    shading_feature_mlp_layer3=args.mlp_layer3)
     if args.checkpoint:
         from .ray_marching import NeuralPoints
-        from .weights import strip_prefix
+        from .weights import block3_layers, strip_prefix
         sd_ = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
         npnts = NeuralPoints.from_state_dict(sd_, dev)
-        r = HipRenderer(npnts.tables(), strip_prefix(sd_), o, dev)
+        r = HipRenderer(npnts.tables(), strip_prefix(sd_, block3_layers=block3_layers(sd_)), o, dev)
     else:
-        pc, mlp = default_scene(args.points)
+        pc, mlp = default_scene(args.points, args.mlp_layer3)
         r = HipRenderer(PointTables.from_cloud(pc, dev), mlp, o, dev)
     views = spiral_views(args.frames, args.h, args.w)
     torch.cuda.synchronize()

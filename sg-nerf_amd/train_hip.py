@@ -65,6 +65,9 @@ class HipTrainer:
         and the backward runs through them on the same split-fp16 GEMMs (train_f32.F32Step)."""
         self.device = torch.device(device)
         self.opts = opts.check_supported()
+        if not opts.block3_layers:
+            raise NotImplementedError("shading_feature_mlp_layer3 = 0 renders only: training this network is not "
+                                      "implemented (it runs on the plain-fp32 kernels, which have no backward)")
         self.variant = tuple(opts.bpnet_variant)
         self.sg = self.variant != (0, 0)
         if precision not in ("f16", "f32"):

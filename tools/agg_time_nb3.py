@@ -1,0 +1,67 @@
+"""Timing probe (not product): config-2 frames (synth-room 1.2 M points, 800x800, SR 64) of the viewmlp
+without block3 (shading_feature_mlp_layer3 = 0) on the plain-fp32 kernels, beside the stock network forced
+onto the same path (HipRenderer.exact = True) for the same frames.  Prints one JSON line per network with
+per-stage HIP-event medians and rays/s.  Usage:
+    python tools/agg_time_nb3.py [frames] [bpnet_layers bpnet_dim]
+On this path sgn_aggregate_exact[_nb3] launches the row kernel and the colour kernel from one call, so the
+"agg" stage is their sum; k_color_exact is the same kernel for both networks, and a kernel trace
+(rocprofv3 --kernel-trace --stats -- python tools/agg_time_nb3.py) splits the two."""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT]
+import sgnerf_amd  # noqa: E402,F401
+from sgnerf_amd import scene  # noqa: E402
+from sgnerf_amd.opts import HotPathOpts  # noqa: E402
+from sgnerf_amd.render import HipRenderer, PointTables  # noqa: E402
+from sgnerf_amd.weights import init_mlp  # noqa: E402
+
+nf = int(sys.argv[1]) if len(sys.argv) > 1 else 6
+nl, dim = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (0, 0)
+dev = "cuda:0"
+pc = scene.synth_room(1_200_000, seed=0)
+if dim:
+    pc = scene.with_semantics(pc, seed=1)
+views = []
+for i in range(2 + nf):
+    yaw, pitch = scene.spiral_yaw_pitch(i % 120, 120)
+    v = scene.room_view(800, 800, yaw=yaw + 15.0, pitch=pitch - 5.0)
+    views.append((torch.from_numpy(v.campos).to(dev), torch.from_numpy(v.camrotc2w).to(dev),
+                  torch.from_numpy(v.raydir).to(dev), v.near, v.far))
+names = ["query", "proj", "agg_rows", "agg_color", "composite", "end"]
+kw = {}
+if dim:   # labels all 0 pass the semantic filter
+    kw = dict(point_labels=torch.zeros(pc.xyz.shape[0], dtype=torch.int32, device=dev),
+              ray_labels=torch.zeros(800 * 800, dtype=torch.int32, device=dev), seconds=5)
+for block3 in (0, 2):
+    mlp = init_mlp(0, bias_std=0.01, bpnet_layers=nl, bpnet_dim=dim, block3_layers=block3)
+    mlp["alpha_branch.0.bias"] = mlp["alpha_branch.0.bias"] + 50.0
+    o = HotPathOpts(SR=64, shading_feature_mlp_layer3=block3, shading_feature_mlp_layer2_bpnet=nl,
+                    predict_semantic=1 if dim else 0, semantic_guidance=1 if dim else 0)
+    tab = PointTables(pc.xyz, pc.embedding, pc.color if block3 else None, pc.dir if block3 else None, pc.conf, dev,
+                      bpnet=pc.bpnet if dim else None)
+    r = HipRenderer(tab, mlp, o, dev)
+    r.exact = True   # the stock network: the plain-fp32 path from the first frame
+    ev = []
+
+    def mark(n):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        ev[-1][n] = e
+
+    for i, (c, rot, rd, ne, fa) in enumerate(views):
+        if i >= 2:
+            ev.append({})
+        r.render(c, rot, rd, ne, fa, marks=mark if i >= 2 else None, check_range=False, **kw)
+    torch.cuda.synchronize()
+    res = {n: float(np.median([e[n].elapsed_time(e[names[j + 1]]) for e in ev])) for j, n in enumerate(names[:-1])}
+    res["agg"] = res.pop("agg_rows") + res.pop("agg_color")   # one call launches both kernels
+    res["frame"] = float(np.median([e["query"].elapsed_time(e["end"]) for e in ev]))
+    res["rays_per_s"] = 800 * 800 / res["frame"] * 1e3
+    res.update(block3_layers=block3, bpnet=[nl, dim], frames=nf, path="plain-fp32")
+    print(json.dumps(res), flush=True)
