@@ -611,6 +611,10 @@ typedef struct {
                            every workgroup copies its block into LDS by DMA instead of converting it */
 } sgn_x3_gemm_args;
 int sgn_x3_gemm(const sgn_x3_gemm_args *g, sgn_stream_t stream);
+/* mode 0 with out[r][n] += the product (+ bias): the second launch of a layer whose inputs exceed K <= 288, on
+ * its remaining weight columns (block2_bpnet.0's 96 BPNet columns).  One-source operand a without activation,
+ * no mask, no out2, K <= 128, an N that runs in 128-wide column blocks (N = 256); *amax_out takes the sums. */
+int sgn_x3_gemm_accumulate(const sgn_x3_gemm_args *g, sgn_stream_t stream);
 size_t sgn_x3_gemm_bpack_bytes(const sgn_x3_gemm_args *g);   /* 0 unless mode 0 with K <= 288 */
 
 /* The f16 training step's row-layer weight gradients (replaces the fp16 GEMMs of the
@@ -643,6 +647,38 @@ int sgn_train_row_inputs(const sgn_point_tables *pt, const sgn_query_out *q, int
  * 16-B aligned tables). */
 int sgn_train_row_gather(const sgn_query_out *q, int32_t K, const int32_t *d_row_off, const int32_t *d_counts,
                          const float *d_src, int32_t dim, float *d_dst, sgn_stream_t stream);
+/* ---- rendering the viewmlp without block3 (shading_feature_mlp_layer3 = 0) on sgn_x3_gemm ----
+ * The row MLP of that network is block1.0, block1.2 (and block2_bpnet.0) as rows-mode sgn_x3_gemm launches over
+ * compact rows, between two small kernels, window by window of the frame's ascending work list (sgn_train_lists):
+ * window w holds the items [w ci, min((w + 1) ci, items)) and the rows of their samples, renumbered from 0, so
+ * every buffer of a window is sized for ci items / ci K rows and reused by the next.
+ *
+ * sgn_rows_windows: d_win[2 w] = window w's item count (<= ci), d_win[2 w + 1] = its row count (<= ci K), for
+ * w < n_win, from d_counts (sgn_train_lists) on the device.  The entries below take one window's two words as
+ * d_win, its first item as item0 and n_items >= its item count (the ci the words were made with); the GEMMs
+ * take &d_win[1] (rows) or &d_win[0] (items) as d_rows.
+ *
+ * sgn_rows_inputs_nb3: sgn_train_row_inputs without block3.0's extras.  Reads neither pt->color nor pt->dir
+ * (both may be NULL) and writes no ext.  Per row j of the window: d_x0[j] fp32[288], d_rw[j] fp32[2]; per item
+ * i of the window: d_vpe[i] fp32[32] (as sgn_train_row_inputs defines them).
+ * sgn_rows_gather_nb3: sgn_train_row_gather over the window (block2_bpnet.0's BPNet rows).
+ * sgn_rows_blend_nb3: the forward head on the last row layer's pre-activation d_z [rows][256]: h_k = LReLU(z_k),
+ * alpha_k = softplus(wa h_k + ba - 1); d_feat[s].x = sum_k w_k alpha_k, d_fs[i][256] = sum_k w_k h_k with
+ * w_k = d_rw[row].x, sums in slot order (deterministic, no atomics).  d_blend / d_wnorm (or NULL) [s K + k]
+ * = d_rw[row] (.x, .y) for k < samp_nnb[s], 0 for the item's other slots -- sgn_aggregate_exact_nb3's values;
+ * slots of samples without a neighbour are not written (the caller clears the buffers once per frame).
+ * *d_flag = +inf's bits (atomicMax, an amax word like sgn_x3_gemm's) when a blended value is not finite or
+ * |f_s| >= 65504. */
+int sgn_rows_windows(const sgn_query_out *q, int32_t K, const int32_t *d_row_off, const int32_t *d_counts, int32_t ci,
+                     int32_t n_win, int32_t *d_win, sgn_stream_t stream);
+int sgn_rows_inputs_nb3(const sgn_point_tables *pt, const sgn_query_out *q, int32_t K, const int32_t *d_row_off,
+                        const int32_t *d_win, int64_t item0, int32_t n_items, float *d_x0, float *d_rw, float *d_vpe,
+                        sgn_stream_t stream);
+int sgn_rows_gather_nb3(const sgn_query_out *q, int32_t K, const int32_t *d_row_off, const int32_t *d_win, int64_t item0,
+                        int32_t n_items, const float *d_src, int32_t dim, float *d_dst, sgn_stream_t stream);
+int sgn_rows_blend_nb3(const sgn_query_out *q, int32_t K, const int32_t *d_row_off, const int32_t *d_win, int64_t item0,
+                       int32_t n_items, const float *d_z, const float *d_rw, const float *d_wa, const float *d_ba,
+                       float *d_feat, float *d_fs, float *d_blend, float *d_wnorm, uint32_t *d_flag, sgn_stream_t stream);
 /* color_branch.6 + sigmoid * 1.002 - 0.001 (fp32) on the items' last hidden layer d_h3 [items][128]
  * (d_w6 [3][128], d_b6 [3]): d_feat[work[i]].rgb. */
 int sgn_train_colour_head(const sgn_query_out *q, const int32_t *d_counts, const float *d_h3, const float *d_w6,

@@ -26,6 +26,14 @@
 //   k_row_tail                     d points_embeding through PE(emb), d colour / dir
 //   k_reduce_partials              partials summed in a fixed order into the flat gradient
 //
+// Rendering the viewmlp without block3 (shading_feature_mlp_layer3 = 0, opts.rows_gemm = 1) reuses the rows
+// mode for its two (with block2_bpnet.0 three) row layers, over windows of the frame's work list:
+//
+//   k_win_counts                   every window's (items, rows) as device words
+//   k_row_inputs<false>            x0, blend weights, PE(viewdir) of a window, rows from 0; no extras
+//   k_row_gather<true>             the window's BPNet rows (k_x3rows<.., ACC> adds their product into zb)
+//   k_rows_blend                   LeakyReLU of the last row layer, the alpha branch, the K-blend: alpha_s, f_s
+//
 // Every GEMM is the 3-product split: x = hi + lo (fp16), w = hi + lo, w x ~ w_hi x_hi + w_hi x_lo +
 // w_lo x_hi on v_mfma_f32_32x32x16_f16 with fp32 accumulation.  Operands are scaled by powers of two
 // before the split so hi stays below 2^14 and lo stays a normal fp16 number: weights by the packer's
@@ -611,8 +619,9 @@ __device__ __forceinline__ ARow<HASP2, ACT> arow(const Opnd &o, const OpRs &rs, 
     return a;
 }
 
-// HASP2: operand A has a second source; ACT: LeakyReLU on A; O2: the launch writes out2 (host-dispatched)
-template <int KS, int WN, bool P1, bool HASP2, bool ACT, bool O2>
+// HASP2: operand A has a second source; ACT: LeakyReLU on A; O2: the launch writes out2 (host-dispatched);
+// ACC: out += the product (a layer whose inputs exceed one weight block's K, run as two launches)
+template <int KS, int WN, bool P1, bool HASP2, bool ACT, bool O2, bool ACC = false>
 __global__ __launch_bounds__(RT_TPB, 1) void k_x3rows(GemmK g) {
     __shared__ __attribute__((aligned(16))) char lds[KS * WN * 2 * FRAG];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -707,10 +716,20 @@ __global__ __launch_bounds__(RT_TPB, 1) void k_x3rows(GemmK g) {
                         mk[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmk, bm, rr * (uint32_t)g.ldm * 4, 0));
                     }
                 }
+                float pv[ACC ? 16 : 1];
+                (void)pv;
+                if constexpr (ACC) {   // the tile's 16 previous values loaded before any is used
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const uint32_t rr = (r & 3) + 8 * (r >> 2);
+                        pv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ro1, b1, rr * (uint32_t)g.ldo * 4, 0));
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const uint32_t rr = (r & 3) + 8 * (r >> 2);
                     float v = acc[t][r] * osc + bv;
+                    if constexpr (ACC) v += pv[r];
                     if (g.mask && (!O2 || o1) && !(mk[r] > 0.f)) v *= 0.01f;
                     const float v1 = g.act ? lrelu_x3(v) : v;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v1), ro1, b1, rr * (uint32_t)g.ldo * 4, 0);
@@ -929,6 +948,11 @@ __device__ __forceinline__ void row_geometry(const RowArgs &a, const Cam &cam, i
 // wave's lanes (row geometry from lane k by a lane-indexed shuffle)
 constexpr int X0_QUADS = 72, ROW_QUADS = 74;
 
+// EXT: block3.0's extra channels (the training step).  Without them (rendering the viewmlp without block3,
+// sgn_rows_inputs_nb3) the kernel reads neither colour nor dir, writes no ext, and works on an item window:
+// a.work points at the window's first item, a.tl at the window's (items, rows) words, and rows land at
+// row_off[s] - row_off[work[0]], so the window's buffers start at row 0.
+template <bool EXT>
 __global__ __launch_bounds__(TPB) void k_row_inputs(RowArgs a, float *x0, float *ext, float2 *rw, float *vpe) {
     // Two items per wave, one per half-wave (lanes 32 h .. 32 h + 31): the items' dependent index chains
     // (work -> sample -> neighbours -> point records) are in flight together, so a wave pays that
@@ -939,11 +963,13 @@ __global__ __launch_bounds__(TPB) void k_row_inputs(RowArgs a, float *x0, float 
     const int wv = blockIdx.x * (TPB / 64) + wl, nw = gridDim.x * (TPB / 64);
     const Cam cam = load_cam(a.campos, a.rot);
     const int n = n_items(a);
+    int rbase = 0;
+    if constexpr (!EXT) rbase = n > 0 ? a.row_off[a.work[0]] : 0;
     for (int i2 = wv; 2 * i2 < n; i2 += nw) {
         const int it = 2 * i2 + h;
         const bool iv = it < n;
         const int s = iv ? a.work[it] : 0;
-        const int nnb = iv ? a.samp_nnb[s] : 0, ro = iv ? a.row_off[s] : 0;
+        const int nnb = iv ? a.samp_nnb[s] : 0, ro = EXT ? (iv ? a.row_off[s] : 0) : (iv ? a.row_off[s] - rbase : 0);
         const int ray = iv ? a.samp_ray[s] : 0;
         // lanes k < K of each half: row k's geometry and weight; normalised over the sample's rows
         const int kl = l32 < a.K ? l32 : 0;
@@ -981,12 +1007,13 @@ __global__ __launch_bounds__(TPB) void k_row_inputs(RowArgs a, float *x0, float 
             *(f32x4 *)&se[wl][h][32 * k + 8 * (l32 & 3) + 4] = e1;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave: its own writes are every lane's
         }
-        const int ntask = nnb * ROW_QUADS;
+        constexpr int RQ = EXT ? ROW_QUADS : X0_QUADS;
+        const int ntask = nnb * RQ;
         const int nmax = max(ntask, __shfl_xor(ntask, 32));
         for (int t0 = 0; t0 < nmax; t0 += 32) {  // wave-uniform trip count: the shuffles see every lane
             const int t = t0 + l32;
             const bool act = t < ntask;
-            const int k = act ? t / ROW_QUADS : 0, q = t - k * ROW_QUADS;
+            const int k = act ? t / RQ : 0, q = t - k * RQ;
             const int pid = __shfl(pidl, 32 * h + k);
             float d[6];
 #pragma unroll
@@ -994,7 +1021,7 @@ __global__ __launch_bounds__(TPB) void k_row_inputs(RowArgs a, float *x0, float 
             if (!act) continue;
             const int64_t row = ro + k;
             const int64_t pb = (int64_t)pid * 3;
-            if (q < X0_QUADS) {
+            if (!EXT || q < X0_QUADS) {
                 *(f32x4 *)(x0 + row * 288 + 4 * q) = x0_quad(4 * q, &se[wl][h][32 * k], d);
             } else if (q == X0_QUADS) {  // block3.0's extra channels (:639-652): colour, dir - v
                 f32x4 u;
@@ -1015,13 +1042,17 @@ __global__ __launch_bounds__(TPB) void k_row_inputs(RowArgs a, float *x0, float 
 }
 
 // d_dst[row] = d_src[pid of the row] (dim floats, as quads): the item's rows x quads as one flat list
+// WIN: an item window (a.work / a.tl as in k_row_inputs<false>): rows relative to the window's first
+template <bool WIN>
 __global__ __launch_bounds__(TPB) void k_row_gather(RowArgs a, const float *src, int dim, float *dst) {
     const int lane = threadIdx.x & 63;
     const int wv = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6), nw = gridDim.x * (TPB / 64);
     const int n = n_items(a), nq = dim >> 2;
+    int rbase = 0;
+    if constexpr (WIN) rbase = n > 0 ? a.row_off[a.work[0]] : 0;
     for (int it = wv; it < n; it += nw) {
         const int s = a.work[it];
-        const int nnb = a.samp_nnb[s], ro = a.row_off[s];
+        const int nnb = a.samp_nnb[s], ro = WIN ? a.row_off[s] - rbase : a.row_off[s];
         for (int t = lane; t < nnb * nq; t += 64) {
             const int k = t / nq, q = t - k * nq;
             const int pid = a.pidx[(int64_t)s * a.K + k];
@@ -1223,6 +1254,91 @@ __global__ __launch_bounds__(TPB) void k_row_head(RowArgs a, float *z4d4, const 
     if (lane == 0) atomicMax(amax, __builtin_bit_cast(uint32_t, am));
 }
 
+// ---- rendering the viewmlp without block3 on the rows GEMM (item windows) -----------------------
+// A frame's work items are cut into windows of ci items; window w's (items, rows) as device words
+// win[2 w], win[2 w + 1]: the row kernels' counts and the GEMMs' d_rows.  Items never exceed ci, rows
+// never ci K, whatever the list holds: the window's buffers are sized by those.
+__global__ __launch_bounds__(TPB) void k_win_counts(const int32_t *tl, const int32_t *work, const int32_t *row_off,
+                                                    const int32_t *nnb, int ci, int K, int nwin, int32_t *win) {
+    const int w = blockIdx.x * TPB + threadIdx.x;
+    if (w >= nwin) return;
+    const int64_t i0 = (int64_t)w * ci;
+    const int64_t left = (int64_t)tl[0] - i0;
+    const int items = left < 0 ? 0 : left > ci ? ci : (int)left;
+    int rows = 0;
+    if (items > 0) {
+        const int s0 = work[i0], s1 = work[i0 + items - 1];
+        rows = row_off[s1] + nnb[s1] - row_off[s0];
+    }
+    win[2 * w] = items;
+    win[2 * w + 1] = min(max(rows, 0), ci * K);
+}
+
+// The forward head of the last row layer z [rows][256] (point_aggregators.py:640-653, :743-770 with block3 =
+// passfunc): h_k = LReLU(z_k); alpha_k = softplus(wa h_k + ba - 1); alpha_s = sum_k w_k alpha_k -> feat[s].x;
+// f_s = sum_k w_k h_k -> fs[item]; the slots' weights -> blend / wnorm [s K + k] (0 on empty slots).  One wave
+// per item of the window, all its rows in flight, the K dot products in one batched reduction (k_row_head's
+// scheme); sums over k in slot order: deterministic.  *flag |= a blended value that is not finite or has left
+// fp16 range (f_s feeds the colour MLP's split-fp16 GEMM).
+constexpr uint32_t RANGE_BITS = 0x7f800000u;   // what a flagged launch leaves in its amax word: +inf
+__global__ __launch_bounds__(TPB) void k_rows_blend(RowArgs a, const float *z, const float2 *rw, const float *wa,
+                                                    const float *ba, float *feat, float *fs, float *blend, float *wnorm,
+                                                    uint32_t *flag) {
+    const int lane = threadIdx.x & 63;
+    const int wv = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6), nw = gridDim.x * (TPB / 64);
+    const int n = n_items(a);
+    if (n <= 0) return;
+    const int rbase = a.row_off[a.work[0]];
+    const f32x4 wa4 = *(const f32x4 *)(wa + 4 * lane);
+    const float bav = ba[0];
+    bool bad = false;
+    for (int it = wv; it < n; it += nw) {
+        const int s = a.work[it];
+        const int nnb = a.samp_nnb[s], ro = a.row_off[s] - rbase;
+        f32x4 h[MAX_K];
+        float red[16];
+#pragma unroll
+        for (int k = 0; k < MAX_K; ++k) {
+            h[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (k < nnb) h[k] = *(const f32x4 *)(z + (int64_t)(ro + k) * 256 + 4 * lane);
+        }
+        const float2 wwl = lane < nnb ? rw[ro + lane] : make_float2(0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < MAX_K; ++k) {
+            float pa = 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                h[k][q] = lrelu(h[k][q]);
+                pa += wa4[q] * h[k][q];
+            }
+            red[k] = pa;
+            red[MAX_K + k] = 0.f;
+        }
+        wave_sum16(red, lane);
+        f32x4 f = {0.f, 0.f, 0.f, 0.f};
+        float as = 0.f;
+#pragma unroll
+        for (int k = 0; k < MAX_K; ++k) {
+            if (k >= nnb) break;
+            const float al = softplus(lane_value(red[0], 4 * k) + bav - 1.f);
+            const float wk = lane_value(wwl.x, k);
+            as += wk * al;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) f[q] += wk * h[k][q];
+        }
+        *(f32x4 *)(fs + (int64_t)it * 256 + 4 * lane) = f;
+        if (lane == 0) feat[(int64_t)s * 4] = as;
+        if (lane < a.K) {
+            if (blend) blend[(int64_t)s * a.K + lane] = wwl.x;
+            if (wnorm) wnorm[(int64_t)s * a.K + lane] = wwl.y;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bad = bad || !(fabsf(f[q]) < 65504.f);
+        bad = bad || !(fabsf(as) < 3.0e38f);
+    }
+    if (__ballot(bad) != 0 && lane == 0) atomicMax(flag, RANGE_BITS);
+}
+
 // the point gradients of a row: d emb through [emb | PE(emb)] (networks.py:175-192) from block1.0's
 // input gradient dx0 [rows][224]; d colour, d dir from block3.0's extra-channel gradient dext
 // [rows][8] (d (dir - v) + v d <dir, v>)
@@ -1399,12 +1515,14 @@ size_t sgn_x3_gemm_bpack_bytes(const sgn_x3_gemm_args *g) {
     return (size_t)nb * ks * (w96 ? 3 : 4) * 2 * sgn::tx::FRAG;
 }
 
-int sgn_x3_gemm(const sgn_x3_gemm_args *ga, sgn_stream_t stream) {
+namespace {
+int x3_gemm(const sgn_x3_gemm_args *ga, sgn_stream_t stream, bool accumulate) {
     using namespace sgn;
     using namespace sgn::tx;
     SGN_REQUIRE(ga, "null argument");
     const sgn_x3_gemm_args &g = *ga;
     SGN_REQUIRE(g.mode == 0 || g.mode == 1, "mode: 0 rows, 1 split-K partials");
+    SGN_REQUIRE(!accumulate || g.mode == 0, "accumulate: mode 0 only");
     SGN_REQUIRE(g.M >= 0 && g.N > 0 && g.K >= 0, "bad extents");
     SGN_REQUIRE(g.a.p && g.b.p, "null operand");
     auto conv = [](const sgn_x3_operand &o, int dyn, int nrows, Opnd &d) -> int {
@@ -1497,6 +1615,19 @@ int sgn_x3_gemm(const sgn_x3_gemm_args *ga, sgn_stream_t stream) {
                 }
             }
         };
+        if (accumulate) {
+            // out += A B^T: the second launch of a layer with more than 288 inputs (block2_bpnet.0's BPNet columns)
+            SGN_REQUIRE(!p1 && !hasp2 && !act && !o2 && !g.mask && ks <= 8 && !w96,
+                        "accumulate: one-source operand a without activation, no mask, no out2, K <= 128, an N that "
+                        "runs in 128-wide column blocks (N = 256)");
+            if (k.bpack) {
+                const int nf = nb * 8 * 4 * 64;
+                hipLaunchKernelGGL((k_x3bpack<8, 4, false>), dim3((nf + TPB - 1) / TPB), dim3(TPB), 0, st, k);
+            }
+            hipLaunchKernelGGL((k_x3rows<8, 4, false, false, false, false, true>), grid, dim3(RT_TPB), 0, st, k);
+            SGN_CHECK_HIP(hipGetLastError());
+            return 0;
+        }
         using I8 = std::integral_constant<int, 8>;
         using I16 = std::integral_constant<int, 16>;
         using I18 = std::integral_constant<int, 18>;
@@ -1546,6 +1677,10 @@ int sgn_x3_gemm(const sgn_x3_gemm_args *ga, sgn_stream_t stream) {
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
 }
+}  // namespace
+
+int sgn_x3_gemm(const sgn_x3_gemm_args *g, sgn_stream_t stream) { return x3_gemm(g, stream, false); }
+int sgn_x3_gemm_accumulate(const sgn_x3_gemm_args *g, sgn_stream_t stream) { return x3_gemm(g, stream, true); }
 
 int sgn_train_lists(const int32_t *d_counters, const int32_t *d_samp_nnb, int64_t s_cap, int32_t *d_work,
                     int32_t *d_row_off, float *d_feat, int32_t *d_counts, void *d_ws, sgn_stream_t stream) {
@@ -1593,7 +1728,7 @@ int sgn_train_row_inputs(const sgn_point_tables *pt, const sgn_query_out *q, int
     SGN_REQUIRE(((uintptr_t)d_x0 & 15) == 0 && ((uintptr_t)d_rw & 7) == 0, "aligned x0 / rw required");
     const RowArgs a = row_args(pt, q, K, d_row_off, d_counts);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_row_inputs, dim3(ROW_GRID), dim3(TPB), 0, st, a, d_x0, d_ext, (float2 *)d_rw, d_vpe);
+    hipLaunchKernelGGL(k_row_inputs<true>, dim3(ROW_GRID), dim3(TPB), 0, st, a, d_x0, d_ext, (float2 *)d_rw, d_vpe);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1608,7 +1743,7 @@ int sgn_train_row_gather(const sgn_query_out *q, int32_t K, const int32_t *d_row
                 "dim % 4 == 0 and 16-B aligned tables");
     RowArgs a{};
     a.work = q->work; a.samp_nnb = q->samp_nnb; a.pidx = q->pidx; a.row_off = d_row_off; a.tl = d_counts; a.K = K;
-    hipLaunchKernelGGL(k_row_gather, dim3(ROW_GRID), dim3(TPB), 0, as_stream(stream), a, d_src, dim, d_dst);
+    hipLaunchKernelGGL(k_row_gather<false>, dim3(ROW_GRID), dim3(TPB), 0, as_stream(stream), a, d_src, dim, d_dst);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1682,6 +1817,95 @@ int sgn_train_row_tail(const sgn_point_tables *pt, const sgn_query_out *q, int32
                                                          k_row_tail<4>, k_row_tail<5>, k_row_tail<6>, k_row_tail<7>};
     hipLaunchKernelGGL(kern[tr], dim3(ROW_GRID), dim3(TPB), 0, as_stream(stream), a, d_dx0, d_dext, grads->embedding,
                        grads->color, grads->dir);
+    SGN_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the viewmlp without block3 on the rows GEMM: item windows ------------------------------------
+namespace {
+// the window's view of the lists: work from its first item, the counts its own (items, rows) words
+sgn::tx::RowArgs window_args(const sgn_query_out *q, int32_t K, const int32_t *row_off, const int32_t *win, int64_t item0) {
+    sgn::tx::RowArgs a{};
+    a.counters = q->counters; a.work = q->work + item0; a.samp_ray = q->samp_ray; a.samp_nnb = q->samp_nnb;
+    a.pidx = q->pidx; a.samp_locw = q->samp_locw; a.row_off = row_off; a.tl = win; a.K = K;
+    return a;
+}
+// one wave per item (k_row_inputs: per two), at most the training step's grid
+int window_grid(int32_t n_items, int per_wave) {
+    const int64_t blocks = ((int64_t)n_items + 4 * per_wave - 1) / (4 * per_wave);
+    return (int)(blocks < 1 ? 1 : blocks > ROW_GRID ? ROW_GRID : blocks);
+}
+}  // namespace
+#define SGN_REQUIRE_WINDOW(q, K, row_off, win, item0, n_items)                                                      \
+    do {                                                                                                            \
+        SGN_REQUIRE((q) && (q)->work && (q)->samp_nnb && (q)->pidx && (row_off) && (win), "null argument");         \
+        SGN_REQUIRE((K) >= 1 && (K) <= 8, "K = 1 .. 8");                                                            \
+        SGN_REQUIRE((item0) >= 0 && (item0) < (1 << 30) && (n_items) >= 1 && (int64_t)(n_items) * (K) < (1 << 30),  \
+                    "item window: item0 >= 0, 1 <= n_items, n_items K < 2^30");                                     \
+    } while (0)
+
+int sgn_rows_windows(const sgn_query_out *q, int32_t K, const int32_t *d_row_off, const int32_t *d_counts, int32_t ci,
+                     int32_t n_win, int32_t *d_win, sgn_stream_t stream) {
+    using namespace sgn;
+    using namespace sgn::tx;
+    SGN_REQUIRE(q && q->work && q->samp_nnb && d_row_off && d_counts && d_win, "null argument");
+    SGN_REQUIRE(K >= 1 && K <= 8, "K = 1 .. 8");
+    SGN_REQUIRE(ci >= 1 && (int64_t)ci * K < (1 << 30) && n_win >= 1 && (int64_t)ci * n_win < ((int64_t)1 << 31),
+                "windows: ci >= 1, ci K < 2^30, n_win >= 1, ci n_win < 2^31");
+    hipLaunchKernelGGL(k_win_counts, dim3((n_win + TPB - 1) / TPB), dim3(TPB), 0, as_stream(stream), d_counts, q->work,
+                       d_row_off, q->samp_nnb, ci, K, n_win, d_win);
+    SGN_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sgn_rows_inputs_nb3(const sgn_point_tables *pt, const sgn_query_out *q, int32_t K, const int32_t *d_row_off,
+                        const int32_t *d_win, int64_t item0, int32_t n_items, float *d_x0, float *d_rw, float *d_vpe,
+                        sgn_stream_t stream) {
+    using namespace sgn;
+    using namespace sgn::tx;
+    SGN_REQUIRE(pt && d_x0 && d_rw && d_vpe, "null argument");
+    SGN_REQUIRE_WINDOW(q, K, d_row_off, d_win, item0, n_items);
+    SGN_REQUIRE(q->samp_ray && q->samp_locw && pt->xyz && pt->embedding && pt->conf, "null query list or point table");
+    SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir && !pt->pers, "camera required, no precomputed pers");
+    SGN_REQUIRE_NO_ROT(pt);
+    SGN_REQUIRE(((uintptr_t)d_x0 & 15) == 0 && ((uintptr_t)d_rw & 7) == 0, "aligned x0 / rw required");
+    RowArgs a = window_args(q, K, d_row_off, d_win, item0);
+    a.xyz = pt->xyz; a.emb = pt->embedding; a.conf = pt->conf;   // colour and dir stay NULL: not read
+    a.campos = pt->campos; a.rot = pt->camrotc2w; a.raydir = pt->raydir;
+    hipLaunchKernelGGL(k_row_inputs<false>, dim3(window_grid(n_items, 2)), dim3(TPB), 0, as_stream(stream), a, d_x0,
+                       (float *)nullptr, (float2 *)d_rw, d_vpe);
+    SGN_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sgn_rows_gather_nb3(const sgn_query_out *q, int32_t K, const int32_t *d_row_off, const int32_t *d_win, int64_t item0,
+                        int32_t n_items, const float *d_src, int32_t dim, float *d_dst, sgn_stream_t stream) {
+    using namespace sgn;
+    using namespace sgn::tx;
+    SGN_REQUIRE(d_src && d_dst, "null argument");
+    SGN_REQUIRE_WINDOW(q, K, d_row_off, d_win, item0, n_items);
+    SGN_REQUIRE(dim > 0 && dim % 4 == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0,
+                "dim % 4 == 0 and 16-B aligned tables");
+    const RowArgs a = window_args(q, K, d_row_off, d_win, item0);
+    hipLaunchKernelGGL(k_row_gather<true>, dim3(window_grid(n_items, 1)), dim3(TPB), 0, as_stream(stream), a, d_src, dim,
+                       d_dst);
+    SGN_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sgn_rows_blend_nb3(const sgn_query_out *q, int32_t K, const int32_t *d_row_off, const int32_t *d_win, int64_t item0,
+                       int32_t n_items, const float *d_z, const float *d_rw, const float *d_wa, const float *d_ba,
+                       float *d_feat, float *d_fs, float *d_blend, float *d_wnorm, uint32_t *d_flag, sgn_stream_t stream) {
+    using namespace sgn;
+    using namespace sgn::tx;
+    SGN_REQUIRE(d_z && d_rw && d_wa && d_ba && d_feat && d_fs && d_flag, "null argument");
+    SGN_REQUIRE_WINDOW(q, K, d_row_off, d_win, item0, n_items);
+    SGN_REQUIRE(((uintptr_t)d_z & 15) == 0 && ((uintptr_t)d_fs & 15) == 0 && ((uintptr_t)d_wa & 15) == 0 &&
+                    ((uintptr_t)d_rw & 7) == 0,
+                "aligned z / fs / wa / rw required");
+    const RowArgs a = window_args(q, K, d_row_off, d_win, item0);
+    hipLaunchKernelGGL(k_rows_blend, dim3(window_grid(n_items, 1)), dim3(TPB), 0, as_stream(stream), a, d_z,
+                       (const float2 *)d_rw, d_wa, d_ba, d_feat, d_fs, d_blend, d_wnorm, d_flag);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -76,6 +76,9 @@ class HipPointsVolumetricModel:
                             help="early ray termination of test renders: transmittance threshold, 0 = off")
         parser.add_argument("--sgn_early_stop_slots", type=str, default="4,8,16",
                             help="slot boundaries at which early ray termination looks at the transmittance")
+        parser.add_argument("--sgn_rows_gemm", type=int, default=0,
+                            help="1: render the viewmlp without block3 (shading_feature_mlp_layer3 = 0) on the "
+                                 "split-fp16 row GEMMs instead of the plain-fp32 kernels")
         return parser
 
     def name(self):
@@ -103,6 +106,8 @@ class HipPointsVolumetricModel:
             extra["early_stop"] = float(opt.sgn_early_stop)
         if hasattr(opt, "sgn_early_stop_slots"):
             extra["early_stop_slots"] = tuple(int(x) for x in str(opt.sgn_early_stop_slots).replace(",", " ").split())
+        if getattr(opt, "sgn_rows_gemm", 0):   # or rows_gemm itself in the namespace (from_opt)
+            extra["rows_gemm"] = int(opt.sgn_rows_gemm)
         # rendering (test / probe) runs the test-mode depth table; the trainer jitters (is_train)
         self.opts = HotPathOpts.from_opt(opt, **extra, is_train=0).check_supported()
         self.model_names = ["ray_marching"]

@@ -110,6 +110,9 @@ class HotPathOpts:
     # channel moves by at most 1.001 * early_stop.  0 = off (every valid sample is aggregated).
     early_stop: float = 0.0
     early_stop_slots: Tuple[int, ...] = (4, 8, 16)   # strictly increasing; boundaries >= SR are ignored
+    # 1: HipRenderer renders the viewmlp without block3 (shading_feature_mlp_layer3 = 0) on the split-fp16 row
+    # GEMMs (sgn_x3_gemm over item windows, render.py) instead of the plain-fp32 kernels.  0 = off.
+    rows_gemm: int = 0
     is_train: int = 0
 
     @property
@@ -217,7 +220,7 @@ class HotPathOpts:
                     if isinstance(v, str):
                         v = tuple(int(x) for x in v.replace(",", " ").split())
                     v = v if isinstance(v, tuple) else (int(v),)
-                if f.name in ("early_stop", "zero_epsilon", "sparse_loss_weight") and v is None:
+                if f.name in ("early_stop", "zero_epsilon", "sparse_loss_weight", "rows_gemm") and v is None:
                     continue
                 kw[f.name] = v
         # argparse's lone default weight beside unset items (color_loss_items None, color_loss_weights [1.0]):
@@ -314,6 +317,16 @@ class HotPathOpts:
         if (not isinstance(sl, tuple) or any(isinstance(x, bool) or not isinstance(x, numbers.Integral) or x <= 0 for x in sl)
                 or any(b <= a for a, b in zip(sl, sl[1:]))):
             bad.append("early_stop_slots must be a tuple of strictly increasing positive slot boundaries")
+        rg = self.rows_gemm
+        if isinstance(rg, bool) or not isinstance(rg, numbers.Integral) or rg not in (0, 1):
+            bad.append("rows_gemm must be 0 or 1")
+        elif rg == 1:
+            if self.shading_feature_mlp_layer3 != 0:
+                bad.append("rows_gemm = 1 renders the viewmlp without block3 only (shading_feature_mlp_layer3 = 0)")
+            if self.precision != "f32":
+                bad.append("rows_gemm = 1 is the split-fp16 fp32-faithful path: precision must be 'f32'")
+            if self.is_train:
+                bad.append("rows_gemm = 1 renders only: not with is_train")
         if bad:
             raise NotImplementedError("; ".join(bad))
         return self

@@ -5,13 +5,14 @@ This is the product path behind NeuralPointsRayMarching.forward (ray_marching.py
 and bench.py.  Buffers are sized once per (R, SR) and reused.
 """
 import ctypes
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import torch
 
 from . import _lib
 from .opts import HotPathOpts
 from .querier import LightningFastQuerier
+from .rows_gemm import RowsGemmNb3
 from .weights import block3_layers, mlp_variant, pack_mlp, strip_prefix
 
 
@@ -93,9 +94,18 @@ class PointTables:
 
 
 class HipRenderer:
-    def __init__(self, points: PointTables, mlp_state, opts: HotPathOpts, device):
+    def __init__(self, points: PointTables, mlp_state, opts: HotPathOpts, device, rows_gemm=None, rows_ci=None):
+        """rows_gemm (0 / 1): overrides opts.rows_gemm -- the viewmlp without block3 on the split-fp16 row GEMMs
+        (rows_gemm.RowsGemmNb3).  rows_ci: that path's window size in work items (default: CI K <= 1 M rows)."""
         self.device = torch.device(device)
+        if rows_gemm is not None:
+            opts = replace(opts, rows_gemm=rows_gemm)
         self.opts = opts.check_supported()
+        if self.opts.rows_gemm and self.opts.K > 8:
+            raise NotImplementedError(f"rows_gemm = 1 holds a sample's rows in one wave: K <= 8, not {self.opts.K}")
+        self._rows_ci = rows_ci
+        self.rows = None           # rows_gemm = 1: the row-GEMM path's weights, window buffers and launch arguments
+        self._rows_frame = False   # the last frame was aggregated on it
         self.points = points
         self.querier = LightningFastQuerier(self.device, opts)
         self.set_mlp(mlp_state)
@@ -120,11 +130,16 @@ class HipRenderer:
                              f"{self.opts.bpnet_variant} (shading_feature_mlp_layer2_bpnet / predict_semantic)")
         self.f32 = self.opts.precision == "f32"
         if not self.block3:
-            # the viewmlp without block3 lives on the plain-fp32 path only (sgn_aggregate_exact_nb3): no split-fp16
+            # the viewmlp without block3 lives on the plain-fp32 path (sgn_aggregate_exact_nb3): no split-fp16
             # blob, no point projection, no fp16-range check, and (as on that path, _tiers) no early-stop tiers
             self.packed = None
             self.packed_exact = pack_mlp(self.mlp_state, self.device, "exact", block3_layers=0)
             self.exact = True
+            if self.opts.rows_gemm:
+                # ... or, opted in, on the split-fp16 row GEMMs, with the plain-fp32 path as the range fallback
+                # (`exact` turns on once a frame's activations left fp16 range) and for rotated points / tiers
+                self.rows = RowsGemmNb3(self.mlp_state, self.variant, self.opts.K, self._rows_ci, self.device)
+                self.exact = False
             return
         self.packed = pack_mlp(self.mlp_state, self.device, self.opts.precision)
         # f32 mode's range fallback: plain fp32 weights for sgn_aggregate_exact, packed on first use; `exact`
@@ -172,6 +187,8 @@ class HipRenderer:
     def _flag(self):
         """The fp16-range flag of the last frame: the workspace word of its colour stage, or, for a frame
         aggregated tier by tier (every tier's colour stage clears that word), the OR over its tiers."""
+        if self._rows_frame:   # the row-GEMM path: its launches' amax words folded into one
+            return self.rows.flag()
         return self.es[3] if self._tiered else self._ws_flag()
 
     def _range_check(self, mode, redo):
@@ -184,6 +201,8 @@ class HipRenderer:
         the renderer to the plain-fp32 path; False: no check."""
         if not self.f32 or not mode or self.exact:
             return
+        if self.rows is not None and not self._rows_frame:
+            return   # rows_gemm = 1, but this frame ran on the plain-fp32 path (rotated points, early-stop tiers)
         if mode == "sync":
             flag = self._flag()
             if int(flag.item()) != 0:
@@ -238,6 +257,10 @@ class HipRenderer:
         (semantic_guidance = 1, worldcoords.py:839-938).  `check_range`: the f32 mode's fp16-range
         guard ("sync" default: a frame whose activations leave fp16 range is re-rendered on the
         plain-fp32 path, sgn_aggregate_exact; "deferred" for pipelined frame loops + finish(), False).
+        The viewmlp without block3 with rows_gemm = 1 follows the same protocol on its own amax words
+        (rows_gemm.RowsGemmNb3.flag, fallback sgn_aggregate_exact_nb3); that path reads the frame's item count
+        on the host once per frame (one small copy and stream sync, whatever check_range says), and renders
+        frames of rotated points and frames the stock network would aggregate tier by tier on the plain-fp32 path.
         `want_probe`: also the per-ray hole-probing records (opt.prob = 1; sgn_probe, RenderOut.probe
         [R, 48]); implies want_opacity and want_blend.  `query_size`: overrides opts.query_size for this
         call (probe_hole's prob_kernel_size); the cached grid is kept.  `want_depth`: also the depth map
@@ -324,7 +347,7 @@ class HipRenderer:
                                               L.sgn_point_proj_bytes(self.points.n))
         if self.block3 and (self._proj is None or self._proj.numel() < nproj):
             self._proj = torch.empty(max(nproj, 16), dtype=torch.uint8, device=self.device)
-        if not self.exact:
+        if not self.exact and self.block3:
             n = self.points.n
             if self._fp is None or self._fp[0] != n:
                 self._fp = (n, torch.zeros(int(L.sgn_frame_points_mark_bytes(n)), dtype=torch.uint8, device=self.device),
@@ -356,6 +379,11 @@ class HipRenderer:
                                            _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate")
 
         tiers = self._tiers(want_probe, want_weights, want_blend)
+        if self.rows is not None:
+            # rows_gemm = 1: the frame on the row GEMMs, unless the plain-fp32 path has to take it: after a range
+            # fallback, with rotated points, and where the stock network would aggregate tier by tier
+            self._rows_frame = not self.exact and self.points.rot is None and not tiers
+            tiers = ()
         self._tiered = bool(tiers)
         if tiers:
             # early ray termination: tier by tier, every launch enqueued without a host sync.  Each tier's
@@ -380,7 +408,11 @@ class HipRenderer:
         else:
             for stage, name in ((1, "agg_rows"), (2, "agg_color")):
                 mark(name)
-                if self.exact:
+                if self._rows_frame:
+                    if stage == 1:
+                        self.rows.run(pt, qo, q, cap, bp, self.feat, self.blend if want_blend else None,
+                                      self.wnorm if want_weights else None)
+                elif self.exact or self.rows is not None:
                     if stage == 1:
                         aggregate_exact()
                 else:

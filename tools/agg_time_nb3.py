@@ -2,8 +2,10 @@
 without block3 (shading_feature_mlp_layer3 = 0) on the plain-fp32 kernels, beside the stock network forced
 onto the same path (HipRenderer.exact = True) for the same frames.  Prints one JSON line per network with
 per-stage HIP-event medians and rays/s.  Usage:
-    python tools/agg_time_nb3.py [frames] [bpnet_layers bpnet_dim]
-On this path sgn_aggregate_exact[_nb3] launches the row kernel and the colour kernel from one call, so the
+    python tools/agg_time_nb3.py [frames] [bpnet_layers bpnet_dim] [--rows_gemm]
+--rows_gemm: also the network without block3 on the split-fp16 row GEMMs (opts.rows_gemm = 1; path "rows-gemm"), on
+the same frames; its "agg" stage is the lists, every window's launches and the colour MLP.
+On the plain-fp32 path sgn_aggregate_exact[_nb3] launches the row kernel and the colour kernel from one call, so the
 "agg" stage is their sum; k_color_exact is the same kernel for both networks, and a kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/agg_time_nb3.py) splits the two."""
 import json
@@ -21,8 +23,10 @@ from sgnerf_amd.opts import HotPathOpts  # noqa: E402
 from sgnerf_amd.render import HipRenderer, PointTables  # noqa: E402
 from sgnerf_amd.weights import init_mlp  # noqa: E402
 
-nf = int(sys.argv[1]) if len(sys.argv) > 1 else 6
-nl, dim = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (0, 0)
+argv = [a for a in sys.argv[1:] if a != "--rows_gemm"]
+rows_gemm = "--rows_gemm" in sys.argv[1:]
+nf = int(argv[0]) if len(argv) > 0 else 6
+nl, dim = (int(argv[1]), int(argv[2])) if len(argv) > 2 else (0, 0)
 dev = "cuda:0"
 pc = scene.synth_room(1_200_000, seed=0)
 if dim:
@@ -38,15 +42,16 @@ kw = {}
 if dim:   # labels all 0 pass the semantic filter
     kw = dict(point_labels=torch.zeros(pc.xyz.shape[0], dtype=torch.int32, device=dev),
               ray_labels=torch.zeros(800 * 800, dtype=torch.int32, device=dev), seconds=5)
-for block3 in (0, 2):
+for block3, rows in [(0, 0)] + ([(0, 1)] if rows_gemm else []) + [(2, 0)]:
     mlp = init_mlp(0, bias_std=0.01, bpnet_layers=nl, bpnet_dim=dim, block3_layers=block3)
     mlp["alpha_branch.0.bias"] = mlp["alpha_branch.0.bias"] + 50.0
     o = HotPathOpts(SR=64, shading_feature_mlp_layer3=block3, shading_feature_mlp_layer2_bpnet=nl,
-                    predict_semantic=1 if dim else 0, semantic_guidance=1 if dim else 0)
+                    predict_semantic=1 if dim else 0, semantic_guidance=1 if dim else 0, rows_gemm=rows)
     tab = PointTables(pc.xyz, pc.embedding, pc.color if block3 else None, pc.dir if block3 else None, pc.conf, dev,
                       bpnet=pc.bpnet if dim else None)
     r = HipRenderer(tab, mlp, o, dev)
-    r.exact = True   # the stock network: the plain-fp32 path from the first frame
+    if not rows:
+        r.exact = True   # the stock network: the plain-fp32 path from the first frame
     ev = []
 
     def mark(n):
@@ -63,5 +68,7 @@ for block3 in (0, 2):
     res["agg"] = res.pop("agg_rows") + res.pop("agg_color")   # one call launches both kernels
     res["frame"] = float(np.median([e["query"].elapsed_time(e["end"]) for e in ev]))
     res["rays_per_s"] = 800 * 800 / res["frame"] * 1e3
-    res.update(block3_layers=block3, bpnet=[nl, dim], frames=nf, path="plain-fp32")
+    res.update(block3_layers=block3, bpnet=[nl, dim], frames=nf, path="rows-gemm" if rows else "plain-fp32")
+    if rows:
+        res.update(window_items=r.rows.ci, items=int(r.rows.counts[0]), rows=int(r.rows.counts[1]), on_path=r._rows_frame)
     print(json.dumps(res), flush=True)
