@@ -758,12 +758,12 @@ __device__ __forceinline__ X3Pair pe_dists16_k(const PeRow &r) {
 // block3.2 epilogue of a tile (K-blend -> f_s, alpha), per lane: rows 4 g + i of half g >> 1
 struct Epi16 {
     float wsa[4], wsb[4];   // the rows' blend weights split by segment (A: positions < nA, B: the rest),
-                            // times 2^-s3 (block3.2's accumulators hold 2^s3 (W x + b))
+                            // times 2^-s3 (block3.2's accumulators hold 2^s3 (W x + b), and LeakyReLU
+                            // commutes with the power of two, so the scale is taken off here, once per row)
     float ap[4];            // alpha partials of the 4 rows over this lane's units
     float fsv[4];           // blended features of units 16 t + r, t = 4 (T / 4) .. + 3, stored per 4
     float *fs_dst;
     bool fs_have;
-    float inv3;
 };
 
 // a workgroup's tiles: first, first + step, ... < end (grid-stride; an XCD-contiguous order measured
@@ -842,22 +842,23 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
         for (int i = 0; i < 4; ++i) {
             const float wi = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((4 * g + i) * 4, __builtin_bit_cast(int, wgt)));
             const bool inA = 4 * (g & 1) + i < nA;
-            e.wsa[i] = inA ? wi : 0.f;
-            e.wsb[i] = inA ? 0.f : wi;
+            const float ws = wi * inv3;  // exact
+            e.wsa[i] = inA ? ws : 0.f;
+            e.wsb[i] = inA ? 0.f : ws;
             e.ap[i] = 0.f;
         }
         e.fs_have = ((g & 1) ? nB > 0 : nA > 0) && ok;
-        e.inv3 = inv3;
         e.fs_dst = (float *)a.fs + (int64_t)((uint32_t)((g & 1) ? ce.y : ce.x) & 0x0FFFFFFFu) * HID + r;
     };
-    // block3.2 output tile T of accumulators `ac` (2^s3 (W x + b)): LeakyReLU, alpha partials, K-blend
+    // block3.2 output tile T of accumulators `ac` (2^s3 (W x + b), started at the bias like every other
+    // layer's): LeakyReLU of the raw accumulator, alpha partials, K-blend -- six instructions per value
     auto epi_step = [&](Epi16 &e, const char *ldsi, const f32x4 (&ac)[16], auto tc) {
         constexpr int T = decltype(tc)::value;
         const float wau = ((const float *)(ldsi + YT16_OFF))[320 + r * 20 + T];  // 2^-s3 alpha weight
         float fa = 0.f, fb = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float hv = lrelu_x3(__builtin_fmaf(ac[T][i], e.inv3, ((const float *)(ldsi + YT16_OFF))[r * 20 + T]));
+            const float hv = lrelu_x3(ac[T][i]);
             e.ap[i] = __builtin_fmaf(wau, hv, e.ap[i]);
             fa = __builtin_fmaf(e.wsa[i], hv, fa);
             fb = __builtin_fmaf(e.wsb[i], hv, fb);
@@ -877,8 +878,9 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
     };
     auto epi_end = [&](Epi16 &e, const char *ldsi, int nA, int nB, int s_ix) {
         // alpha: row logits summed over the 16 lanes (units) of the group, softplus(x + b - 1), blended
-        // over the segment's rows like f_s
+        // over the segment's rows like f_s (the weights carry 2^-s3: taken off the sum, exactly)
         const float ba = ((const float *)(ldsi + YR_OFF))[Y_BA];
+        const float sc3 = __builtin_bit_cast(float, 0x7F000000 - __builtin_bit_cast(int, ((const float *)(ldsi + YR_OFF))[Y_INV + 3]));
         float xr[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -903,7 +905,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
             asb = __builtin_fmaf(e.wsb[i], sp4[i], asb);
         }
         permlane16_swap(asa, asb);
-        const float as = asa + asb;  // even groups: A's alpha, odd groups: B's
+        const float as = (asa + asb) * sc3;  // even groups: A's alpha, odd groups: B's
         // the segment's sample: row 0 (A) or row max(nA, 4) (B) of the half (lanes 0..15 hold rows)
         const int s_of = __builtin_amdgcn_ds_bpermute((8 * (g >> 1) + ((g & 1) ? (nA > 4 ? nA : 4) : 0)) * 4, s_ix);
         if (r == 0 && ((g & 1) ? nB > 0 : nA > 0)) a.feat[(int64_t)s_of * 4 + 0] = as;
@@ -1077,10 +1079,17 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
         });
         // block3.2: 256 -> 256 transposed: acc[t][i] = h[row 4 g + i][unit 16 t + (l & 15)]
         auto &acc = in2;  // block3.0's input is dead: its registers take block3.2's accumulators
+        {   // the accumulators start at 2^s3 b3 of the lane's units 16 t + r (the transposed LDS copy)
+            const f32x4 *yb = (const f32x4 *)(ldsi + YT16_OFF + r * 80);
 #pragma unroll
-        for (int q = 0; q < NS; ++q)
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 b4 = yb[j];
 #pragma unroll
-            for (int t = 0; t < 16; ++t) acc[q][t] = f32x4{};  // the bias joins in the epilogue (epi_step)
+                for (int q = 0; q < NS; ++q)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[q][4 * j + i] = f32x4{b4[i], b4[i], b4[i], b4[i]};
+            }
+        }
         // the next tile's record (and this tile's slot entry for the epilogue: half g >> 1's
         // {A item | nA << 28, B item | nB << 28, ..}) go out at the end of block3.2's first chunk, after
         // the chunk's DMA pieces, so they stay in flight across one boundary (VmL3P0)
@@ -1233,8 +1242,8 @@ void layout_blob16(int ksb, int bpnet_dim, Pairs &&pairs, F32 &&f32) {
         f32(Y_B0 + u, YK_BS, 0, u);
         f32(Y_B1 + u, YK_BS, 1, u);
         f32(Y_B2 + u, YK_BS, 2, u);
-        f32(Y_B3 + u, YK_B, 3, u);  // block3.2's bias, added in the row kernel's epilogue
-        f32(Y_WA + u, YK_W, 4, u);
+        f32(Y_B3 + u, YK_BS, 3, u);
+        f32(Y_WA + u, YK_WINV, 4, u);  // the alpha dot reads block3.2's activations still scaled by 2^s3
     }
     f32(Y_BA, YK_B, 4, 0);
     const int li[7] = {0, 1, 2, 3, 5, 6, 7};

@@ -20,6 +20,8 @@ mlp_x3.hip:
            chunk-boundary waits and barriers, its output layer
   v_mix / v_early / v_early3 / v_epic / e_order: schedule experiments that were measured and not kept
            (each described at its patch below)
+  epi_fma  block3.2's bias added in the epilogue (fma per value) instead of started from
+           (the product's earlier code, for the same-box A/B of DESIGN 3.1, exposed VALU)
 train_x3.hip:
   tx_tn2 / tx_tn3: weight-gradient GEMM at two workgroups per CU (256 x 64 / 128 x 96 blocks)
   txa_nostage / txa_nomfma: k_x3rows without its weight staging loads, its MFMAs
@@ -34,7 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "sg-nerf_amd", "csrc")
 
 MLP_PATCHES = ("timing", "timing2", "tdump", "abl_dma", "abl_bar", "abl_conv", "abl_epi", "abl_pe", "cabl_dma",
-               "cabl_bar", "cabl_out", "v_mix", "v_early", "v_early3", "v_epic", "e_order")
+               "cabl_bar", "cabl_out", "v_mix", "v_early", "v_early3", "v_epic", "e_order", "epi_fma")
 TX_PATCHES = ("tx_tn2", "tx_tn3", "txa_nostage", "txa_nomfma", "dwa_noconv")
 
 
@@ -304,35 +306,30 @@ __device__ __forceinline__ void dma_dup(const WBlob &wb, char *dst, int lane) {
                     return o;
                 }, NoHook{}, first_chunk_loads);''')
     elif p == "v_epic":
-        # the epilogue's per-lane constants (block3.2 bias and alpha weight of unit 16 T + r, T = 0..15) read
-        # into registers once per tile (8 ds_read_b128, one wait) instead of one LDS read + wait per step
-        s = rep(s, '''    float inv3;
-};''', '''    float inv3;
+        # the epilogue's per-lane constants (the alpha weight of unit 16 T + r, T = 0..15) read into registers
+        # once per tile (4 ds_read_b128, one wait) instead of one LDS read + wait per step
+        s = rep(s, '''    bool fs_have;
+};''', '''    bool fs_have;
 };
 struct EpiC {
-    float b[16], wa[16];
+    float wa[16];
 };''')
         s = rep(s, '''    auto epi_step = [&](Epi16 &e, const char *ldsi, const f32x4 (&ac)[16], auto tc) {
         constexpr int T = decltype(tc)::value;
         const float wau = ((const float *)(ldsi + YT16_OFF))[320 + r * 20 + T];  // 2^-s3 alpha weight''',
                 '''    EpiC ec;
     auto epi_consts = [&](const char *ldsi) {
-        const f32x4 *yb = (const f32x4 *)(ldsi + YT16_OFF + r * 80), *yw = (const f32x4 *)(ldsi + YT16_OFF + 1280 + r * 80);
+        const f32x4 *yw = (const f32x4 *)(ldsi + YT16_OFF + 1280 + r * 80);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const f32x4 u = yb[j], v = yw[j];
+            const f32x4 v = yw[j];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ec.b[4 * j + i] = u[i];
-                ec.wa[4 * j + i] = v[i];
-            }
+            for (int i = 0; i < 4; ++i) ec.wa[4 * j + i] = v[i];
         }
     };
     auto epi_step = [&](Epi16 &e, const char *ldsi, const f32x4 (&ac)[16], auto tc) {
         constexpr int T = decltype(tc)::value;
         const float wau = ec.wa[T];  // 2^-s3 alpha weight''')
-        s = rep(s, '''            const float hv = lrelu_x3(__builtin_fmaf(ac[T][i], e.inv3, ((const float *)(ldsi + YT16_OFF))[r * 20 + T]));''',
-                '''            const float hv = lrelu_x3(__builtin_fmaf(ac[T][i], e.inv3, ec.b[T]));''')
         s = rep(s, '''            for (int q = 0; q < NS; ++q) epi_begin(e[q], ldsi, rw[q].wgt, nA[q], nB[q], ce[q], eslot[q] < nslots);''',
                 '''            for (int q = 0; q < NS; ++q) epi_begin(e[q], ldsi, rw[q].wgt, nA[q], nB[q], ce[q], eslot[q] < nslots);
             epi_consts(ldsi);''')
@@ -414,6 +411,18 @@ struct EpiC {
 #pragma unroll
                     for (int s = 0; s < NS; ++s) acc[s][AOFF + t] = mfma16(Ah, B.b[s].hi, acc[s][AOFF + t]);
                 }''')
+    elif p == "epi_fma":
+        s = rep(s, "            const float hv = lrelu_x3(ac[T][i]);\n",
+                "            const float hv = lrelu_x3(__builtin_fmaf(ac[T][i], inv3e, ((const float *)(ldsi + YT16_OFF))[r * 20 + T]));\n")
+        s = rep(s, '''        const float wau = ((const float *)(ldsi + YT16_OFF))[320 + r * 20 + T];  // 2^-s3 alpha weight''',
+                '''        const float wau = ((const float *)(ldsi + YT16_OFF))[320 + r * 20 + T];
+        const float inv3e = ((const float *)(ldsi + YR_OFF))[Y_INV + 3];''')
+        s = rep(s, "            const float ws = wi * inv3;  // exact\n", "            const float ws = wi;\n")
+        s = rep(s, "        const float as = (asa + asb) * sc3;", "        const float as = asa + asb;")
+        s = rep(s, "for (int i = 0; i < 4; ++i) acc[q][4 * j + i] = f32x4{b4[i], b4[i], b4[i], b4[i]};",
+                "for (int i = 0; i < 4; ++i) acc[q][4 * j + i] = f32x4{};")
+        s = rep(s, "        f32(Y_B3 + u, YK_BS, 3, u);\n        f32(Y_WA + u, YK_WINV, 4, u);",
+                "        f32(Y_B3 + u, YK_B, 3, u);\n        f32(Y_WA + u, YK_W, 4, u);")
     elif p == "abl_pe":
         s = rep(s, '''                    for (int q = 0; q < NS; ++q) o.b[q] = pe_dists16_k<decltype(k)::value>(pr[q]);''',
                 '''                    for (int q = 0; q < NS; ++q) {
