@@ -19,8 +19,9 @@ class FlatMLP(nn.Module):
 
     def __init__(self, state, device, layers=LAYERS):
         super().__init__()
-        state = strip_prefix(state)
         self.layers = list(layers)
+        # a layer list without block3.* is the viewmlp without block3 (weights.layers_for(block3_layers=0))
+        state = strip_prefix(state, block3_layers=2 if any(n.startswith("block3.") for n, *_ in self.layers) else 0)
         parts, self.slices, off = [], {}, 0
         for name, o, i, _ in self.layers:
             parts += [torch.as_tensor(state[name + ".weight"]).float().reshape(-1),
@@ -57,8 +58,20 @@ class _PackerF32:
 
     YK_ZERO, YK_W, YK_B, YK_BS, YK_INV, YK_ONE, YK_WINV = range(7)
 
-    def __init__(self, device, mlp: "FlatMLP", variant=(0, 0)):
+    def __init__(self, device, mlp: "FlatMLP", variant=(0, 0), shifts_only=False):
+        """shifts_only: a layer list k_rows16 has no blob for (the viewmlp without block3): `pack` writes the
+        per-layer shifts the split-fp16 GEMMs read and nothing else (sgn_pack_scaled_f32 without sections, the call
+        rows_gemm.RowsGemmNb3 makes once per weight set), and returns None."""
         L = _lib.lib()
+        self.shifts_only = bool(shifts_only)
+        if self.shifts_only:
+            nl = self.n_layers = len(mlp.layers)
+            assert nl <= 16
+            self.woff = (ctypes.c_int64 * nl)(*[mlp.slices[n][0] for n, *_ in mlp.layers])
+            self.wlen = (ctypes.c_int64 * nl)(*[mlp.slices[n][1] * mlp.slices[n][2] for n, *_ in mlp.layers])
+            self.shift = torch.zeros(16, dtype=torch.int32, device=device)
+            self.blob = None
+            return
         self.n16b = int(L.sgn_mlp_layout_f32(0))
         n32 = int(L.sgn_mlp_layout_f32(1))
         self.total = int(L.sgn_mlp_packed_bytes_f32(*variant))
@@ -112,6 +125,11 @@ class _PackerF32:
         """Per-layer shifts and both blob sections from the flat parameter: two launches."""
         flat = flat.detach()
         assert flat.is_contiguous() and flat.dtype == torch.float32
+        if self.shifts_only:   # one launch, no host read: the weights change every step
+            _lib.check(_lib.lib().sgn_pack_scaled_f32(_lib.ptr(flat), flat.numel(), self.n_layers, self.woff, self.wlen,
+                                                      None, 0, None, 0, _lib.ptr(self.shift), None, None,
+                                                      _lib.stream_handle()), "sgn_pack_scaled_f32 (shifts)")
+            return None
         _lib.check(_lib.lib().sgn_pack_scaled_f32(
             _lib.ptr(flat), flat.numel(), self.n_layers, self.woff, self.wlen, _lib.ptr(self.code16), self.code16.numel(),
             _lib.ptr(self.code32), self.code32.numel(), _lib.ptr(self.shift), _lib.ptr(self.blob[:self.n16b]),

@@ -79,6 +79,9 @@ class HipPointsVolumetricModel:
         parser.add_argument("--sgn_rows_gemm", type=int, default=0,
                             help="1: render the viewmlp without block3 (shading_feature_mlp_layer3 = 0) on the "
                                  "split-fp16 row GEMMs instead of the plain-fp32 kernels")
+        parser.add_argument("--sgn_train_rows", type=int, default=0,
+                            help="1: train the viewmlp without block3 (shading_feature_mlp_layer3 = 0) with the fp32 "
+                                 "step on the split-fp16 row GEMMs; 0: training that network is refused")
         return parser
 
     def name(self):
@@ -108,6 +111,8 @@ class HipPointsVolumetricModel:
             extra["early_stop_slots"] = tuple(int(x) for x in str(opt.sgn_early_stop_slots).replace(",", " ").split())
         if getattr(opt, "sgn_rows_gemm", 0):   # or rows_gemm itself in the namespace (from_opt)
             extra["rows_gemm"] = int(opt.sgn_rows_gemm)
+        if getattr(opt, "sgn_train_rows", 0):  # or train_rows itself in the namespace (from_opt)
+            extra["train_rows"] = int(opt.sgn_train_rows)
         # rendering (test / probe) runs the test-mode depth table; the trainer jitters (is_train)
         self.opts = HotPathOpts.from_opt(opt, **extra, is_train=0).check_supported()
         self.model_names = ["ray_marching"]
@@ -190,8 +195,9 @@ class HipPointsVolumetricModel:
             self.setup_optimizer(self.opt)
 
     def _check_trainable(self):
-        """The viewmlp without block3 renders only (the plain-fp32 kernels have no backward)."""
-        if not self.opts.block3_layers:
+        """The viewmlp without block3 renders only (the plain-fp32 kernels have no backward) unless the options
+        carry train_rows = 1 (the fp32 step on the row GEMMs, train_f32.F32StepNb3)."""
+        if not self.opts.block3_layers and not self.opts.train_rows:
             raise NotImplementedError("shading_feature_mlp_layer3 = 0 renders only: training this network is not "
                                       "implemented (it runs on the plain-fp32 kernels, which have no backward)")
 
@@ -234,15 +240,19 @@ class HipPointsVolumetricModel:
         # the step at the model's arithmetic: precision "f32" (the reference's) trains through the
         # fp32-faithful forward and the fp32 backward (base viewmlp and SG's block2_bpnet alike)
         prec = "f16" if self.opts.precision == "f16" else "f32"
+        # the rendering options stay as they are (test frames may render with rows_gemm = 1, which does not
+        # combine with is_train); the trainer's are its own
         self.trainer = HipTrainer(params, self.net_ray_marching.renderer.mlp_state,
-                                  dataclasses.replace(self.opts, is_train=1), self.device,
+                                  dataclasses.replace(self.opts, is_train=1, rows_gemm=0), self.device,
                                   lr=g("lr", 5e-4), plr=g("plr", 2e-3), lr_decay_exp=g("lr_decay_exp", 0.1),
                                   lr_decay_iters=g("lr_decay_iters", 1_000_000), bpnet=bp, precision=prec)
         # the renderer reads the trained tensors in place (views; the table cache follows their versions)
         n = params.xyz.shape[0]
         npnt.points_embeding = params.points_embeding.detach().view(1, n, -1)
-        npnt.points_color = params.points_color.detach().view(1, n, 3)
-        npnt.points_dir = params.points_dir.detach().view(1, n, 3)
+        if params.points_color is not None:   # without block3 a cloud may carry neither
+            npnt.points_color = params.points_color.detach().view(1, n, 3)
+        if params.points_dir is not None:
+            npnt.points_dir = params.points_dir.detach().view(1, n, 3)
         npnt.points_conf = params.points_conf.detach().view(1, n, 1)
         self.optimizers = [self.trainer.opt_net, self.trainer.opt_pts]
         self.schedulers = []
@@ -292,8 +302,9 @@ class HipPointsVolumetricModel:
         mask = p.points_conf[0, :, 0] >= thresh
         keep = lambda t: None if t is None or t.shape[-2 if t.dim() == 3 else 0] != mask.shape[0] else (  # noqa: E731
             t[:, mask] if t.dim() == 3 else t[mask])
-        self.neural_points = NeuralPoints(p.xyz[mask], p.points_embeding[:, mask], p.points_color[:, mask],
-                                          p.points_dir[:, mask], p.points_conf[:, mask], self.device,
+        sel = lambda t: None if t is None else t[:, mask]  # noqa: E731  (no colour / dir: without block3)
+        self.neural_points = NeuralPoints(p.xyz[mask], p.points_embeding[:, mask], sel(p.points_color),
+                                          sel(p.points_dir), p.points_conf[:, mask], self.device,
                                           points_feats=keep(p.points_feats), points_label=keep(p.points_label),
                                           bpnet_points_embedding=keep(p.bpnet_points_embedding),
                                           Rw2c=p.Rw2c[mask] if p.Rw2c.dim() == 3 else p.Rw2c)  # :540-542
@@ -311,6 +322,10 @@ class HipPointsVolumetricModel:
         [3,3] Rw2c covers the new points as it is."""
         self._sync_weights()
         p = self.neural_points
+        missing = [k for k in ("points_color", "points_dir") if getattr(p, k) is None]
+        if missing:
+            raise NotImplementedError(f"grow_points on a cloud without {' and '.join(missing)}: the new points' "
+                                      "tensors have nothing to be appended to")
         Rw2c = p.Rw2c
         if Rw2c.dim() == 3:
             m = torch.as_tensor(add_xyz).reshape(-1, 3).shape[0]

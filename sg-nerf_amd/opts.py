@@ -113,6 +113,9 @@ class HotPathOpts:
     # 1: HipRenderer renders the viewmlp without block3 (shading_feature_mlp_layer3 = 0) on the split-fp16 row
     # GEMMs (sgn_x3_gemm over item windows, render.py) instead of the plain-fp32 kernels.  0 = off.
     rows_gemm: int = 0
+    # 1: HipTrainer trains the viewmlp without block3 (shading_feature_mlp_layer3 = 0) with the fp32 step on the
+    # split-fp16 row GEMMs (train_f32.F32StepNb3).  0 = off: training that network stays refused.
+    train_rows: int = 0
     is_train: int = 0
 
     @property
@@ -129,10 +132,18 @@ class HotPathOpts:
         return int(self.shading_feature_mlp_layer3)
 
     @property
+    def _train_rows_on(self):
+        """train_rows is the integer 1 (True, 1.0 and "1" are refused, not taken for it)."""
+        tr = self.train_rows
+        return not isinstance(tr, bool) and isinstance(tr, numbers.Integral) and tr == 1
+
+    @property
     def trained_points(self):
-        """The trained point tensors' names, in the point Adam group's order."""
-        sw = (("points_embeding", self.feat_grad), ("points_color", self.color_grad), ("points_dir", self.dir_grad),
-              ("points_conf", self.conf_grad))
+        """The trained point tensors' names, in the point Adam group's order.  Without block3 the points' colour
+        and dir are outside the network's graph (point_aggregators.py:356-368): frozen whatever their switches say."""
+        nb3 = not self.block3_layers
+        sw = (("points_embeding", self.feat_grad), ("points_color", 0 if nb3 else self.color_grad),
+              ("points_dir", 0 if nb3 else self.dir_grad), ("points_conf", self.conf_grad))
         return tuple(name for name, v in sw if v)
 
     @property
@@ -220,7 +231,7 @@ class HotPathOpts:
                     if isinstance(v, str):
                         v = tuple(int(x) for x in v.replace(",", " ").split())
                     v = v if isinstance(v, tuple) else (int(v),)
-                if f.name in ("early_stop", "zero_epsilon", "sparse_loss_weight", "rows_gemm") and v is None:
+                if f.name in ("early_stop", "zero_epsilon", "sparse_loss_weight", "rows_gemm", "train_rows") and v is None:
                     continue
                 kw[f.name] = v
         # argparse's lone default weight beside unset items (color_loss_items None, color_loss_weights [1.0]):
@@ -251,7 +262,7 @@ class HotPathOpts:
             # the viewmlp without block3 (point_aggregators.py:356-368) renders on the plain-fp32 kernels only
             if self.precision == "f16":
                 bad.append("shading_feature_mlp_layer3 = 0 is rendered in plain fp32 only: precision must be 'f32', not 'f16'")
-            if self.is_train:
+            if self.is_train and not self._train_rows_on:
                 bad.append("shading_feature_mlp_layer3 = 0 renders only: training (is_train) is not implemented")
         if self.shading_feature_mlp_layer2_bpnet not in (0, 1):
             bad.append("block2_bpnet: at most one layer (shading_feature_mlp_layer2_bpnet 0 or 1)")
@@ -327,6 +338,15 @@ class HotPathOpts:
                 bad.append("rows_gemm = 1 is the split-fp16 fp32-faithful path: precision must be 'f32'")
             if self.is_train:
                 bad.append("rows_gemm = 1 renders only: not with is_train")
+        tr = self.train_rows
+        if isinstance(tr, bool) or not isinstance(tr, numbers.Integral) or tr not in (0, 1):
+            bad.append("train_rows must be 0 or 1")
+        elif tr == 1:
+            if self.shading_feature_mlp_layer3 != 0:
+                bad.append("train_rows = 1 trains the viewmlp without block3 only (shading_feature_mlp_layer3 = 0): the "
+                           "stock network trains on its own step")
+            if self.precision != "f32":
+                bad.append("train_rows = 1 is the fp32 step on the split-fp16 row GEMMs: precision must be 'f32'")
         if bad:
             raise NotImplementedError("; ".join(bad))
         return self

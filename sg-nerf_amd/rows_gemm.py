@@ -24,13 +24,10 @@ import ctypes
 import torch
 
 from . import _lib
-from .train_f32 import _addr, _operand, _rows_gemm
-from .weights import BPNET, layers_for
+from .train_f32 import FP16_RANGE_BITS, GEMM_BYTES_LIMIT, X0_LD, _addr, _operand, _rows_gemm, row_forward_gemms
+from .weights import layers_for
 
-X0_LD = 288                      # block1.0's input row (284 inputs, the ones column, padding)
-GEMM_BYTES_LIMIT = 0x7fffffff    # sgn_x3_gemm mode 0: 32-bit buffer offsets, every operand below 2 GiB
 ROWS_DEFAULT = 1 << 20           # rows of a default window (CI K <= 1 M rows: x0 1.2 GB, z1 / z2 1 GB each)
-FP16_RANGE_BITS = 0x477FE000     # 65504.0f: an amax word at or above it has left fp16 range
 
 
 def max_window_rows(ld=X0_LD):
@@ -143,21 +140,10 @@ class RowsGemmNb3:
         rows, ci = self.rows, self.ci
         x0, z1, z2 = _addr(self.x0), _addr(self.z[0]), _addr(self.z[1])
         W, S, B = self.W, self.S, self.B
-        w10, o, i = W("block1.0")
-        G = [_rows_gemm(_operand(x0, X0_LD, X0_LD, 0), _operand(w10, i, i, 0, shift=S("block1.0")), rows, o, i, n_rows,
-                        z1, 256, bias=B("block1.0"), amax_out=am[self.A_Z1])]
-        w12, o, i = W("block1.2")
-        G.append(_rows_gemm(_operand(z1, 256, 256, 0, act=1), _operand(w12, i, i, 0, shift=S("block1.2")), rows, o, i,
-                            n_rows, z2, 256, bias=B("block1.2"), amax_out=am[self.A_Z2]))
-        acc = None
-        if self.variant[0]:
-            wb, o, i = W(BPNET)
-            G.append(_rows_gemm(_operand(z2, 256, 256, 0, act=1), _operand(wb, i, 256, 0, shift=S(BPNET)), rows, o, 256,
-                                n_rows, z1, 256, bias=B(BPNET), amax_out=am[self.A_ZB]))
-            if self.variant[1]:
-                d = self.variant[1]
-                acc = _rows_gemm(_operand(_addr(self.bprows), d, d, 0), _operand(wb + 256 * 4, i, d, 0, shift=S(BPNET)),
-                                 rows, o, d, n_rows, z1, 256, amax_out=am[self.A_ZB])
+        # block2_bpnet.0's pre-activation reuses z1's buffer: a rendered frame reads z1 no more
+        G, acc = row_forward_gemms(W, B, S, self.variant, rows, n_rows, x0, z1, z2, z1,
+                                   _addr(self.bprows) if self.variant[1] else None,
+                                   (am[self.A_Z1], am[self.A_Z2], am[self.A_ZB]))
         fsa, vpa = _addr(self.fs), _addr(self.vpe)
         h1, h2, h3 = (_addr(t) for t in self.h)
         wc, o, i = W("color_branch.0")

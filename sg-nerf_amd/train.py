@@ -38,7 +38,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .opts import HotPathOpts
-from .weights import LAYERS, strip_prefix
+from .weights import block3_layers, layers_for, strip_prefix
 
 
 def _pe(x, freqs, ori=False):
@@ -51,13 +51,16 @@ def _pe(x, freqs, ori=False):
 
 
 class ViewMLP(nn.Module):
-    """The ScanNet viewmlp parameters under the reference names (block1.0.weight, ...)."""
+    """The ScanNet viewmlp parameters under the reference names (block1.0.weight, ...).  The layer list is the
+    state's: one without block3.* keys is the viewmlp without block3 (shading_feature_mlp_layer3 = 0)."""
 
     def __init__(self, state):
         super().__init__()
-        state = strip_prefix(state)
+        nb3 = block3_layers(state)
+        state = strip_prefix(state, block3_layers=nb3)
+        self.layers = layers_for(block3_layers=nb3)
         self.lin = nn.ModuleDict()
-        for name, o, i, _ in LAYERS:
+        for name, o, i, _ in self.layers:
             m = nn.Linear(i, o)
             with torch.no_grad():
                 m.weight.copy_(torch.as_tensor(state[name + ".weight"]))
@@ -75,7 +78,7 @@ class ViewMLP(nn.Module):
 
     def state(self):
         out = {}
-        for name, *_ in LAYERS:
+        for name, *_ in self.layers:
             m = self.lin[name.replace(".", "_")]
             out[name + ".weight"] = m.weight.detach()
             out[name + ".bias"] = m.bias.detach()
@@ -83,7 +86,8 @@ class ViewMLP(nn.Module):
 
 
 class PointParams(nn.Module):
-    """Trainable neural-point parameters (neural_points.py:370-414 names)."""
+    """Trainable neural-point parameters (neural_points.py:370-414 names).  color / dir may be None for the
+    viewmlp without block3, which reads neither: the attribute is then None."""
 
     def __init__(self, xyz, embedding, color, dir, conf, device):
         super().__init__()
@@ -91,8 +95,8 @@ class PointParams(nn.Module):
         self.register_buffer("xyz", torch.as_tensor(xyz).to(**f).reshape(-1, 3).contiguous())
         n = self.xyz.shape[0]
         self.points_embeding = nn.Parameter(torch.as_tensor(embedding).to(**f).reshape(n, -1).clone())
-        self.points_color = nn.Parameter(torch.as_tensor(color).to(**f).reshape(n, 3).clone())
-        self.points_dir = nn.Parameter(torch.as_tensor(dir).to(**f).reshape(n, 3).clone())
+        self.points_color = None if color is None else nn.Parameter(torch.as_tensor(color).to(**f).reshape(n, 3).clone())
+        self.points_dir = None if dir is None else nn.Parameter(torch.as_tensor(dir).to(**f).reshape(n, 3).clone())
         self.points_conf = nn.Parameter(torch.as_tensor(conf).to(**f).reshape(n, 1).clone())
 
 
@@ -144,7 +148,8 @@ def _dw_rows(gz, x, chunk=DW_CHUNK_F32):
 def aggregate(points: PointParams, mlp: ViewMLP, campos, rot, raydir, samp_ray, samp_locw, pidx):
     """Differentiable PointAggregator.forward on sample-major neighbours.
     Returns feat [S,4] (alpha, r, g, b; zeros for samples without neighbours), conf_coefficient
-    [S,K] (straight-through clamp) and the neighbour mask [S,K].
+    [S,K] (straight-through clamp) and the neighbour mask [S,K].  An mlp without block3 (its layer list holds
+    no block3.*) skips block3 and reads neither points_color nor points_dir (point_aggregators.py:356-368, :638-653).
 
     Every masked selection goes through the valid rows s * K + k (torch.nonzero of pidx >= 0: one
     host sync), by index_select / index_copy (no further syncs)."""
@@ -174,10 +179,11 @@ def aggregate(points: PointParams, mlp: ViewMLP, campos, rot, raydir, samp_ray, 
     x = torch.cat([emb, _pe(emb, 3), _pe(dists.reshape(-1, 6).index_select(0, rows), 5)], dim=-1)
     lr_ = lambda t: F.leaky_relu(t, 0.01)  # noqa: E731
     h = lr_(_linear(mlp, "block1.2", lr_(_linear(mlp, "block1.0", x))))
-    sd = torch.index_select(points.points_dir, 0, fm)
-    ov = ori_v[:, None, :].expand(S, K, 3).reshape(-1, 3).index_select(0, rows)
-    h = torch.cat([h, torch.index_select(points.points_color, 0, fm), sd - ov, torch.sum(sd * ov, dim=-1, keepdim=True)], dim=-1)
-    h = lr_(_linear(mlp, "block3.2", lr_(_linear(mlp, "block3.0", h)), split=True))
+    if any(name.startswith("block3.") for name, *_ in mlp.layers):
+        sd = torch.index_select(points.points_dir, 0, fm)
+        ov = ori_v[:, None, :].expand(S, K, 3).reshape(-1, 3).index_select(0, rows)
+        h = torch.cat([h, torch.index_select(points.points_color, 0, fm), sd - ov, torch.sum(sd * ov, dim=-1, keepdim=True)], dim=-1)
+        h = lr_(_linear(mlp, "block3.2", lr_(_linear(mlp, "block3.0", h)), split=True))
     alpha = F.softplus(mlp.f("alpha_branch.0", h) - 1)
     hk = torch.zeros(S * K, h.shape[-1], device=h.device, dtype=h.dtype).index_copy(0, rows, h)
     ak = torch.zeros(S * K, 1, device=h.device, dtype=h.dtype).index_copy(0, rows, alpha)
@@ -485,14 +491,21 @@ class Trainer:
         self.device = torch.device(device)
         self.opts = opts
         self.points = points
+        if not block3_layers(mlp_state) and not getattr(opts, "train_rows", 0):
+            raise NotImplementedError("shading_feature_mlp_layer3 = 0 renders only: training this network is not "
+                                      "implemented (opts.train_rows = 1 trains it)")
         self.mlp = ViewMLP(mlp_state).to(self.device)
         self.net_params = list(self.mlp.parameters())
-        self.point_params = [points.points_embeding, points.points_color, points.points_dir, points.points_conf]
+        # (without block3 the points may carry no colour and no dir: None)
+        self.point_params = [p for p in (points.points_embeding, points.points_color, points.points_dir,
+                                         points.points_conf) if p is not None]
         # opt.feat_grad / color_grad / dir_grad / conf_grad, the reference's way (neural_points.py:410-416):
         # requires_grad off, the tensor still listed in the group (torch's Adam skips it: no gradient)
         trained = getattr(opts, "trained_points", None)
         for name in ("points_embeding", "points_color", "points_dir", "points_conf"):
             p = getattr(points, name)
+            if p is None:
+                continue
             p.requires_grad_(trained is None or name in trained)
             if not p.requires_grad:
                 p.grad = None

@@ -27,6 +27,11 @@ row_off[s] .. row_off[s] + samp_nnb[s]); items are the samples with a neighbour,
 step's captured graph (train_f16.F16Step) runs the same stage on its own items.  `F32Runner` is what
 train_hip.HipTrainer drives: it keeps the F32Step of the current batch capacity, the projection
 buffer and the step's touched-point list.
+
+`F32StepNb3` / `F32RunnerNb3` are the step of the viewmlp without block3 (shading_feature_mlp_layer3 = 0,
+opts.train_rows = 1): the row MLP's forward runs on the rows-mode GEMMs the renderer's rows_gemm path uses
+(`row_forward_gemms`, shared with rows_gemm.RowsGemmNb3), the head, the backward chain and the weight
+gradients on the launches above with block3 left out.
 """
 import ctypes
 import os
@@ -35,6 +40,7 @@ import torch
 
 from . import _lib, loss_hip
 from .train import gather_counts, touched_rows
+from .weights import BPNET
 
 # split-K partials of the weight-gradient GEMMs (rows / items cut into this many 32-aligned runs;
 # 84 x 3 column blocks = one workgroup per CU for the row layers).  SGN_SPLITS_ROWS / _ITEMS
@@ -89,6 +95,39 @@ def _attach_bpack(gemms, device):
     for g in rows:
         g.bpack = buf.data_ptr()
     return buf
+
+
+X0_LD = 288                      # block1.0's input row (284 inputs, the ones column, padding)
+GEMM_BYTES_LIMIT = 0x7fffffff    # sgn_x3_gemm mode 0: 32-bit buffer offsets, every operand below 2 GiB
+FP16_RANGE_BITS = 0x477FE000     # 65504.0f: an amax word at or above it has left fp16 range
+
+
+def row_forward_gemms(W, B, S, variant, rows, n_rows, x0, z1, z2, zb, bprows, amax):
+    """The rows-mode forward launches of the row MLP without block3 over compact rows, for the renderer's windows
+    (rows_gemm.RowsGemmNb3) and the training step (F32StepNb3) alike:
+        z1 = x0 W10^T + b10;  z2 = LReLU(z1) W12^T + b12;  block2_bpnet.0: zb = LReLU(z2) Wb[:, :256]^T + bb
+    and, with the BPNet columns, the sgn_x3_gemm_accumulate launch zb += bprows Wb[:, 256:]^T.
+    W / B / S: name -> (weight address, out, in) / bias address / shift address; rows: the buffers' row capacity,
+    n_rows: the address of the device row count; x0 [rows, 288], z1, z2, zb [rows, 256], bprows [rows, dim]:
+    addresses (zb / bprows unused without their layer); amax: the addresses of z1's, z2's and zb's amax words.
+    Returns (the two or three launches in order, the accumulate launch or None)."""
+    a_z1, a_z2, a_zb = amax
+    w10, o, i = W("block1.0")
+    G = [_rows_gemm(_operand(x0, X0_LD, X0_LD, 0), _operand(w10, i, i, 0, shift=S("block1.0")), rows, o, i, n_rows,
+                    z1, 256, bias=B("block1.0"), amax_out=a_z1)]
+    w12, o, i = W("block1.2")
+    G.append(_rows_gemm(_operand(z1, 256, 256, 0, act=1), _operand(w12, i, i, 0, shift=S("block1.2")), rows, o, i,
+                        n_rows, z2, 256, bias=B("block1.2"), amax_out=a_z2))
+    acc = None
+    if variant[0]:
+        wb, o, i = W(BPNET)
+        G.append(_rows_gemm(_operand(z2, 256, 256, 0, act=1), _operand(wb, i, 256, 0, shift=S(BPNET)), rows, o, 256,
+                            n_rows, zb, 256, bias=B(BPNET), amax_out=a_zb))
+        if variant[1]:
+            d = variant[1]
+            acc = _rows_gemm(_operand(bprows, d, d, 0), _operand(wb + 256 * 4, i, d, 0, shift=S(BPNET)),
+                             rows, o, d, n_rows, zb, 256, amax_out=a_zb)
+    return G, acc
 
 
 class _FlatAddr:
@@ -490,9 +529,14 @@ class F32Runner:
         if self.key != key:
             self.step, self.key = F32Step(tr, q, R), key
         lo, full, mask, b.depth_map = self.step.run(pt, self.proj, self._blob, b.campos, b.rot, b.gt, b.bg_ray, b.depth)
-        parts = loss_hip.loss_parts(tr.opts, lo, b.depth is not None)
-        parts["total"] = tr.opts.total_loss(parts, None if b.depth is None else b.depth.weight)
-        return parts, full, mask
+        return self._parts(b, lo), full, mask
+
+    def _parts(self, b, lo):
+        """The reported loss parts and their total from the step's loss vector."""
+        opts = self.tr.opts
+        parts = loss_hip.loss_parts(opts, lo, b.depth is not None)
+        parts["total"] = opts.total_loss(parts, None if b.depth is None else b.depth.weight)
+        return parts
 
     def dp_rows(self):
         """Under DP: this rank's touched rows and every rank's count (gathered and read here: the
@@ -500,3 +544,201 @@ class F32Runner:
         return self._t_idx, [int(x) for x in gather_counts(self._t_cnt).tolist()]
 
 
+class F32StepNb3:
+    """F32Step for the viewmlp without block3 (shading_feature_mlp_layer3 = 0; point_aggregators.py:356-368,
+    :638-653): device buffers and pre-built launch arguments for one batch capacity.  No point projection and no
+    blob: the row MLP's forward is the renderer's rows_gemm sequence (row_forward_gemms) over ONE window holding
+    the whole work list, so the window's two device words are the launches' counts and nothing is sized by a host
+    read.  z1, z2 and zb keep a buffer each (the backward reads all of them); the head (sgn_train_row_head) runs on
+    the last of z2 / zb and leaves its delta there.
+
+      lists          sgn_train_lists, sgn_rows_windows (ci = cap, one window)
+      row inputs     sgn_rows_inputs_nb3 -> x0, rw, vpe; 352-input block2_bpnet.0: sgn_rows_gather_nb3 -> bprow
+      row forward    z1, z2 (, zb; sgn_x3_gemm_accumulate on the BPNet columns), sgn_rows_blend_nb3 -> alpha_s, f_s
+      colour         ColourStage.forward_and_loss, ColourStage.backward
+      head           sgn_train_row_head in place on z2 / zb -> delta, d conf, alpha_branch.0's partials
+      row backward   (d2 = delta_b Wb[:, :256] masked by z2,) d1 = d2 W12 masked by z1, dx0 = d1 W10[:, :224]
+      point grads    sgn_train_row_tail (embedding only: colour and dir are outside this network's graph)
+      weight grads   d2^T [LReLU(z1) | 1], d1^T x0 (, delta_b^T [LReLU(z2) | bprow | 1]), one sgn_reduce_partials
+    """
+
+    # amax words after the colour stage's three: the deltas', then the forward's (max |z|, the blend's flag)
+    A_D2, A_D1, A_DB, A_Z1, A_Z2, A_ZB, A_HEAD = range(3, 10)
+
+    def __init__(self, trainer, q, R):
+        L = _lib.lib()
+        o = trainer.opts
+        self.trainer, self.R, self.K = trainer, R, o.K
+        self.sg, self.D = trainer.sg, trainer.variant[1]
+        dev = trainer.device
+        self.cap = cap = max(R * o.SR, 1)
+        self.rows_cap = rows = cap * o.K
+        if rows * X0_LD * 4 + X0_LD * 4 >= GEMM_BYTES_LIMIT:
+            raise ValueError(f"a batch of {R} rays x {o.SR} samples x K = {o.K} holds {rows} rows: the row GEMMs' "
+                             f"operands stay below 2 GiB ({(GEMM_BYTES_LIMIT - 1) // (X0_LD * 4) - 1} rows)")
+        self.q = q
+        self.qo = q.abi()
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.row_off = torch.zeros(cap, **i32)
+        self.counts = torch.zeros(4, **i32)
+        self.win = torch.zeros(2, **i32)           # the one window's (items, rows)
+        self.lists_ws = torch.empty(int(L.sgn_train_lists_workspace_bytes(cap)), dtype=torch.uint8, device=dev)
+        self.feat = torch.zeros(cap, 4, **f32)
+        self.x0 = torch.empty(rows, X0_LD, **f32)
+        self.rw = torch.empty(rows, 2, **f32)
+        self.vpe = torch.empty(cap, 32, **f32)
+        self.fs = torch.empty(cap, 256, **f32)
+        self.z1 = torch.empty(rows, 256, **f32)
+        self.z2 = torch.empty(rows, 256, **f32)    # base: the head leaves delta2 here
+        self.zb = self.d2 = self.bprow = None
+        if self.sg:   # block2_bpnet.0's pre-activation (the head leaves delta_b here), block1.2's delta
+            self.zb = torch.empty(rows, 256, **f32)
+            self.d2 = torch.empty(rows, 256, **f32)
+            self.bprow = torch.empty(rows, self.D, **f32) if self.D else None
+        self.zlast = self.zb if self.sg else self.z2
+        self.d1 = torch.empty(rows, 256, **f32)
+        # block1.0's input gradient feeds d points_embeding alone: frozen, neither the buffer nor its GEMM exists
+        self.dx0 = torch.empty(rows, 224, **f32) if "points_embeding" in trainer.trained else None
+        self.amax = torch.zeros(16, dtype=torch.int32, device=dev)
+        self.dfeat = torch.empty(cap, 4, **f32)
+        self.colour = ColourStage(trainer, self.qo, R, cap, _addr(self.counts, 0), self.fs, self.vpe, self.feat,
+                                  self.dfeat, self.amax)
+        self.part_rows = [torch.empty(SPLITS_ROWS, 256, n, **f32)
+                          for n in (257, 285) + ((257 + self.D,) if self.sg else ())]
+        self.part_a = torch.empty(int(L.sgn_train_head_partial_floats(1)), **f32)
+        self.range_word = None   # after run: int64 [1], non-zero when the forward left fp16 range
+        self._build()
+
+    # -- the launch arguments (pointers of persistent buffers: built once) ----------------------
+    def _build(self):
+        A = _FlatAddr(self.trainer)
+        W, Bv, S = A.W, A.B, A.S
+        amax = [_addr(self.amax, i) for i in range(16)]
+        n_rows = _addr(self.win, 1)
+        rc = self.rows_cap
+        z1, z2, d1 = _addr(self.z1), _addr(self.z2), _addr(self.d1)
+        # ---- row forward: the renderer's launches, every pre-activation in its own buffer ---------
+        self.g_fwd, self.g_acc = row_forward_gemms(W, Bv, S, self.trainer.variant, rc, n_rows, _addr(self.x0), z1, z2,
+                                                   _addr(self.zb) if self.sg else None,
+                                                   _addr(self.bprow) if self.D else None,
+                                                   (amax[self.A_Z1], amax[self.A_Z2], amax[self.A_ZB]))
+        # ---- row backward chain -------------------------------------------------------------------
+        G = []
+        if self.sg:   # the head's delta is block2_bpnet.0's: block1.2's through Wb's first 256 columns
+            db, d2 = _addr(self.zb), _addr(self.d2)
+            self.a_head = self.A_DB
+            w, o_, i_ = W(BPNET)
+            G.append(("d2", _rows_gemm(_operand(db, 256, 256, 0, amax=amax[self.A_DB]),
+                                       _operand(w, i_, 256, 1, shift=S(BPNET)), rc, 256, 256, n_rows, d2, 256,
+                                       mask=z2, ldm=256, amax_out=amax[self.A_D2])))
+        else:         # the head left block1.2's delta in z2's buffer
+            d2 = z2
+            self.a_head = self.A_D2
+        w, o_, i_ = W("block1.2")
+        G.append(("d1", _rows_gemm(_operand(d2, 256, 256, 0, amax=amax[self.A_D2]), _operand(w, i_, i_, 1, shift=S("block1.2")),
+                                   rc, 256, 256, n_rows, d1, 256, mask=z1, ldm=256, amax_out=amax[self.A_D1])))
+        w, o_, i_ = W("block1.0")
+        if self.dx0 is not None:
+            G.append(("dx0", _rows_gemm(_operand(d1, 256, 256, 0, amax=amax[self.A_D1]),
+                                        _operand(w, i_, 224, 1, shift=S("block1.0")), rc, 224, 256, n_rows,
+                                        _addr(self.dx0), 224)))
+        self.g_row_bwd = G
+        # ---- row weight gradients: delta^T [x | 1] ---------------------------------------------
+        pr = self.part_rows
+        self.g_row_dw = [
+            _splitk_gemm(_operand(d2, 256, 256, 1, amax=amax[self.A_D2]), _operand(z1, 256, 256, 1, ones_col=256, act=1),
+                         256, 257, rc, n_rows, _addr(pr[0]), SPLITS_ROWS),
+            _splitk_gemm(_operand(d1, 256, 256, 1, amax=amax[self.A_D1]), _operand(_addr(self.x0), X0_LD, 285, 1),
+                         256, 285, rc, n_rows, _addr(pr[1]), SPLITS_ROWS)]
+        if self.sg:   # block2_bpnet.0: delta_b^T [LReLU(z2) | BPNet embedding | 1]
+            D = self.D
+            xb = (_operand(z2, 256, 256 + D, 1, p2=_addr(self.bprow), ld2=D, csplit=256, ones_col=256 + D, act=1) if D
+                  else _operand(z2, 256, 256, 1, ones_col=256, act=1))
+            self.g_row_dw.append(_splitk_gemm(_operand(_addr(self.zb), 256, 256, 1, amax=amax[self.A_DB]), xb, 256, 257 + D,
+                                              rc, n_rows, _addr(pr[2]), SPLITS_ROWS))
+        # ---- partials -> flat gradient: the colour stage's segments, then the rows' ----------------
+        segs = self.colour.segments + [
+            A.segment(_addr(self.part_a), self.part_a.numel() // 257, 1, 257, "alpha_branch.0", 256, 256),
+            A.segment(_addr(pr[0]), SPLITS_ROWS, 256, 257, "block1.2", 256, 256),
+            A.segment(_addr(pr[1]), SPLITS_ROWS, 256, 285, "block1.0", 284, 284)]
+        if self.sg:
+            segs.append(A.segment(_addr(pr[2]), SPLITS_ROWS, 256, 257 + self.D, BPNET, 256 + self.D, 256 + self.D))
+        self.segs = (_lib.PartialSegment * len(segs))(*segs)
+        self.n_seg = len(segs)
+        self.wa, self.ba = W("alpha_branch.0")[0], Bv("alpha_branch.0")
+        every = (self.colour.gemms + self.g_fwd + ([self.g_acc] if self.g_acc is not None else []) +
+                 [gs for _, gs in self.g_row_bwd] + self.g_row_dw)
+        self.bpack = _attach_bpack(every, A.flat.device)
+
+    # -- one step ------------------------------------------------------------------------------
+    def run(self, pt, campos, rot, gt, bg_ray, depth=None):
+        """F32Step.run for this network: forward + backward of one batch after the query into flat.grad and the
+        point gradients; returns ColourStage.results_out's copies.  self.range_word is the step's fp16-range word."""
+        L = _lib.lib()
+        st = _lib.stream_handle()
+        tr, K, qo, col = self.trainer, self.K, self.qo, self.colour
+        P = tr.points
+        ck = _lib.check
+        cap, p = self.cap, _lib.ptr
+        Q, PT = ctypes.byref(qo), ctypes.byref(pt)
+
+        def gemm(gs):
+            ck(L.sgn_x3_gemm(ctypes.byref(gs), st), "sgn_x3_gemm")
+
+        self.amax.zero_()
+        ck(L.sgn_train_lists(p(self.q.counters), p(self.q.samp_nnb), cap, p(self.q.work), p(self.row_off), p(self.feat),
+                             p(self.counts), p(self.lists_ws), st), "sgn_train_lists")
+        ck(L.sgn_rows_windows(Q, K, p(self.row_off), p(self.counts), cap, 1, p(self.win), st), "sgn_rows_windows")
+        win = p(self.win)
+        ck(L.sgn_rows_inputs_nb3(PT, Q, K, p(self.row_off), win, 0, cap, p(self.x0), p(self.rw), p(self.vpe), st),
+           "sgn_rows_inputs_nb3")
+        if self.D:
+            ck(L.sgn_rows_gather_nb3(Q, K, p(self.row_off), win, 0, cap, p(tr.bpnet32), self.D, p(self.bprow), st),
+               "sgn_rows_gather_nb3")
+        for gs in self.g_fwd:
+            gemm(gs)
+        if self.g_acc is not None:
+            ck(L.sgn_x3_gemm_accumulate(ctypes.byref(self.g_acc), st), "sgn_x3_gemm_accumulate")
+        ck(L.sgn_rows_blend_nb3(Q, K, p(self.row_off), win, 0, cap, p(self.zlast), p(self.rw), self.wa, self.ba,
+                                p(self.feat), p(self.fs), None, None, ctypes.c_void_p(_addr(self.amax, self.A_HEAD)), st),
+           "sgn_rows_blend_nb3")
+        col.forward_and_loss(campos, rot, gt, bg_ray, st, depth)
+        col.backward(st)
+        ck(L.sgn_train_row_head(PT, Q, K, p(self.row_off), p(self.counts), p(self.zlast), p(col.dfs), p(self.dfeat),
+                                p(self.rw), self.wa, self.ba, p(P.points_conf.grad),
+                                ctypes.c_void_p(_addr(self.amax, self.a_head)), p(self.part_a), st), "sgn_train_row_head")
+        for _, gs in self.g_row_bwd:
+            gemm(gs)
+        grads = tr.point_grads()   # the embedding's gradient or NULL: colour and dir are never trained here
+        ck(L.sgn_train_row_tail(PT, Q, K, p(self.row_off), p(self.counts), p(self.dx0), None, ctypes.byref(grads), st),
+           "sgn_train_row_tail")
+        for gs in self.g_row_dw:
+            gemm(gs)
+        ck(L.sgn_reduce_partials(self.n_seg, self.segs, st), "sgn_reduce_partials")
+        # max |z1|, |z2|, |zb| and the blend's flag folded into one word, on the device
+        self.range_word = (self.amax[self.A_Z1:self.A_HEAD + 1].max() >= FP16_RANGE_BITS).to(torch.int64).reshape(1)
+        return col.results_out(col.losses, depth is not None)
+
+
+class F32RunnerNb3(F32Runner):
+    """F32Runner for the viewmlp without block3 (opts.train_rows = 1).  `begin` is F32Runner's (the per-layer
+    shifts recomputed on the device -- the packer is shifts-only, there is no blob -- and the point Adam's launch)
+    after a look, without waiting, at the last step's fp16-range word (train_hip._Watch: a word whose copy has not
+    landed yet is reported a step later); `run` is F32StepNb3.run, with no projection."""
+
+    def begin(self, b):
+        self.tr._range_watch.check()
+        super().begin(b)
+
+    def run(self, b):
+        tr = self.tr
+        q, R = b.q, b.R
+        pt = tr._tables(b.campos, b.rot, b.raydir)
+        fl = tr.mlp.flat
+        key = (R, q.work.data_ptr(), q.pidx.data_ptr(), fl.data_ptr(), fl.grad.data_ptr())
+        if self.key != key:
+            self.step, self.key = F32StepNb3(tr, q, R), key
+        lo, full, mask, b.depth_map = self.step.run(pt, b.campos, b.rot, b.gt, b.bg_ray, b.depth)
+        tr._range_watch.post(self.step.range_word)
+        return self._parts(b, lo), full, mask

@@ -34,6 +34,10 @@ anything but the ScanNet colour weights without a sparse loss runs sgn_loss_trai
 Which point tensors train follows opts.feat_grad / color_grad / dir_grad / conf_grad (neural_points.py:410-416):
 a frozen tensor's gradient pointer is NULL at the C ABI (no kernel computes it), it is in no point-Adam group
 and the data-parallel row exchange does not carry it.
+
+The viewmlp without block3 (shading_feature_mlp_layer3 = 0) trains with opts.train_rows = 1 at precision "f32"
+(train_f32.F32RunnerNb3 / F32StepNb3): the points' colour and dir are outside that network's graph,
+so they may be missing (None) and are treated as frozen tensors whatever their switches say.
 """
 from types import SimpleNamespace
 
@@ -51,6 +55,47 @@ from .weights import layers_for
 POINT_TENSORS = ("points_embeding", "points_color", "points_dir", "points_conf")
 
 
+class _Watch:
+    """A device word (int64 [1]) on its way to pinned host memory without a sync: `post` queues the asynchronous
+    copy, `check` reads a copy that has landed (wait: any pending one) and raises RuntimeError(message, formatted
+    with n = the word) when it is not 0.  `post` first looks at the previous copy without waiting and then reuses the
+    one pinned word, so a word whose copy has not landed by the next `post` is replaced unread.  accumulate: the
+    posted words are first folded (max) into a running device word, which is what travels, so a non-zero word is
+    still in every later copy until a `check` has raised it (the running word is cleared then)."""
+
+    def __init__(self, device, message, accumulate=False):
+        cuda = device.type == "cuda"
+        self.message = message
+        self._host = torch.zeros(1, dtype=torch.int64, pin_memory=cuda)
+        self._event = torch.cuda.Event() if cuda else None
+        self._pending = False
+        self._acc = torch.zeros(1, dtype=torch.int64, device=device) if accumulate else None
+
+    def post(self, word):
+        self.check()
+        word = word.reshape(1)
+        if self._acc is not None:
+            torch.maximum(self._acc, word, out=self._acc)
+            word = self._acc
+        self._host.copy_(word, non_blocking=True)
+        self._event.record()
+        self._pending = True
+
+    def check(self, wait=False):
+        if not self._pending:
+            return
+        if not self._event.query():   # the copy has not landed yet
+            if not wait:
+                return
+            self._event.synchronize()
+        self._pending = False
+        n = int(self._host[0])
+        if n:
+            if self._acc is not None:
+                self._acc.zero_()
+            raise RuntimeError(self.message.format(n=n))
+
+
 class HipTrainer:
     """One data-parallel training step per call on the HIP path (config 5)."""
 
@@ -65,16 +110,20 @@ class HipTrainer:
         and the backward runs through them on the same split-fp16 GEMMs (train_f32.F32Step)."""
         self.device = torch.device(device)
         self.opts = opts.check_supported()
-        if not opts.block3_layers:
+        if not opts.block3_layers and not opts.train_rows:
             raise NotImplementedError("shading_feature_mlp_layer3 = 0 renders only: training this network is not "
                                       "implemented (it runs on the plain-fp32 kernels, which have no backward)")
+        self.nb3 = not opts.block3_layers   # the viewmlp without block3 on the fp32 row-GEMM step (train_rows = 1)
+        if self.nb3 and precision != "f32":
+            raise NotImplementedError("train_rows = 1 trains the viewmlp without block3 with the fp32 step only: "
+                                      f"precision must be 'f32', not {precision!r}")
         self.variant = tuple(opts.bpnet_variant)
         self.sg = self.variant != (0, 0)
         if precision not in ("f16", "f32"):
             raise ValueError("precision: 'f16' or 'f32'")
         self.precision = precision
         self.points = points
-        self.mlp = FlatMLP(mlp_state, self.device, layers_for(*self.variant))
+        self.mlp = FlatMLP(mlp_state, self.device, layers_for(*self.variant, block3_layers=opts.block3_layers))
         self.bpnet16 = self.bpnet32 = None
         if self.variant[1]:
             if bpnet is None:
@@ -88,7 +137,8 @@ class HipTrainer:
         # opt.feat_grad / color_grad / dir_grad / conf_grad (neural_points.py:410-416): a frozen tensor takes
         # no gradient (its kernels' outputs are NULL), has no Adam moments and never changes;
         # point_params are the trained ones, in the point group's order
-        every = {k: getattr(points, k) for k in POINT_TENSORS}
+        # (without block3 colour and dir may be missing -- None -- and are never trained: opts.trained_points)
+        every = {k: getattr(points, k) for k in POINT_TENSORS if getattr(points, k) is not None}
         self.trained = self.opts.trained_points
         for k, p in every.items():
             p.requires_grad_(k in self.trained)
@@ -118,21 +168,31 @@ class HipTrainer:
         self.bucket_elems = bucket_mb * (1 << 20) // 4
         self.querier = querier
         self._last_q = None
-        self.packer = _Packer(self.device, self.variant)
+        # (without block3 there is neither MFMA blob: the packer writes the shifts alone)
+        self.packer = None if self.nb3 else _Packer(self.device, self.variant)
         # the fp32-faithful blob (f32 step) and, for both precisions, the per-layer weight shifts the
         # split-fp16 GEMMs of the colour MLP read
-        self.packer32 = _PackerF32(self.device, self.mlp, self.variant)
+        self.packer32 = _PackerF32(self.device, self.mlp, self.variant, shifts_only=self.nb3)
         # the OOB watch: the out-of-range neighbour count of a step, on its way to pinned host memory
-        self._oob_host = torch.zeros(1, dtype=torch.int64, pin_memory=cuda)
-        self._oob_event = torch.cuda.Event() if cuda else None
-        self._oob_pending = False
+        self._oob = _Watch(self.device, "training step: {n} neighbour indices >= n_points (query and point tables "
+                                        "disagree)")
         # without a row-sparse Adam launch the OOB count comes from sgn_touched_points' stamp table
         self._stamp = self._tlist = self._tcount = None
         self._stamp_n, self._tstep = -1, 0
         # f16: the loss stage replays as a captured HIP graph; False runs the same stage eagerly (torch
         # autograd of the colour MLP into the HIP loss stage), the graph's parity reference in the tests
         self.use_graph = True
-        if precision == "f32":
+        if self.nb3:
+            from .train_f32 import F32RunnerNb3
+            # the fp16-range watch: a step whose row forward left fp16 range is reported at the next step whose
+            # `begin` finds the copy landed (or in check_touched()); the flags are folded into a running device
+            # word, so one whose copy was replaced before it was read is reported with the following step's
+            self._range_watch = _Watch(self.device, "training step (train_rows): the row MLP's forward left fp16 range "
+                                                    "(|activation| >= 65504 or not finite): the split-fp16 row GEMMs "
+                                                    "cannot carry these weights, the step's gradients are not to be "
+                                                    "trusted", accumulate=True)
+            self.stepper = F32RunnerNb3(self)
+        elif precision == "f32":
             from .train_f32 import F32Runner
             self.stepper = F32Runner(self)
         else:
@@ -161,8 +221,9 @@ class HipTrainer:
     def _tables(self, campos, rot, raydir):
         pt = _lib.PointTables()
         P = self.points
-        pt.xyz, pt.embedding, pt.color = P.xyz.data_ptr(), P.points_embeding.data_ptr(), P.points_color.data_ptr()
-        pt.dir, pt.conf, pt.n_points = P.points_dir.data_ptr(), P.points_conf.data_ptr(), P.xyz.shape[0]
+        addr = lambda t: None if t is None else t.data_ptr()  # noqa: E731  (NULL: no colour / dir, without block3)
+        pt.xyz, pt.embedding, pt.color = P.xyz.data_ptr(), P.points_embeding.data_ptr(), addr(P.points_color)
+        pt.dir, pt.conf, pt.n_points = addr(P.points_dir), P.points_conf.data_ptr(), P.xyz.shape[0]
         pt.campos, pt.camrotc2w, pt.raydir = campos.data_ptr(), rot.data_ptr(), raydir.data_ptr()
         return pt
 
@@ -171,27 +232,19 @@ class HipTrainer:
         """The out-of-range neighbour count (a device int64) goes to pinned host memory without a sync;
         the next step (or check_touched()) reads it once the copy has landed and fails loudly on a
         query / point table mismatch (those points would never be projected or updated)."""
-        self._check_oob()
-        self._oob_host.copy_(count.reshape(1), non_blocking=True)
-        self._oob_event.record()
-        self._oob_pending = True
+        self._oob.post(count)
 
     def _check_oob(self, wait=False):
         """Raise if an earlier step's query named a point index >= n_points (sgn_touched_points'
         counter d_count2[2]); without wait only a copy that has already landed is read."""
-        if not self._oob_pending:
-            return
-        if not wait and not self._oob_event.query():
-            return
-        self._oob_event.synchronize()
-        self._oob_pending = False
-        n = int(self._oob_host[0])
-        if n:
-            raise RuntimeError(f"training step: {n} neighbour indices >= n_points (query and point tables disagree)")
+        self._oob.check(wait)
 
     def check_touched(self):
-        """Wait for and check the last step's out-of-range neighbour counter (see _check_oob)."""
+        """Wait for and check the last step's out-of-range neighbour counter (see _check_oob) and, without
+        block3, its fp16-range word."""
         self._check_oob(wait=True)
+        if self.nb3:
+            self._range_watch.check(wait=True)
 
     def touched_points(self, q):
         """The step's touched points (sgn_touched_points: an int32 list in no particular order and its
@@ -216,8 +269,8 @@ class HipTrainer:
         return self._tlist, self._tcount[step & 1]
 
     def point_grads(self):
-        """The point gradients as the kernels take them (sgn_point_grads): NULL for a frozen tensor."""
-        g = [getattr(self.points, k).grad for k in POINT_TENSORS]
+        """The point gradients as the kernels take them (sgn_point_grads): NULL for a frozen or missing tensor."""
+        g = [getattr(getattr(self.points, k), "grad", None) for k in POINT_TENSORS]
         return _lib.PointGrads(*[None if t is None else t.data_ptr() for t in g])
 
     # -- row-sparse point Adam --------------------------------------------------------------
@@ -341,7 +394,7 @@ def grads_named(trainer: HipTrainer):
         out[name + ".weight"] = m.w(name, g).detach().clone()
         out[name + ".bias"] = m.b(name, g).detach().clone()
     P = trainer.points
-    for k in POINT_TENSORS:   # a frozen tensor has none
-        g = getattr(P, k).grad
+    for k in POINT_TENSORS:   # a frozen (or missing) tensor has none
+        g = getattr(getattr(P, k), "grad", None)
         out[k] = None if g is None else g.detach().clone()
     return out
