@@ -813,6 +813,13 @@ __global__ void __launch_bounds__(256) k_compact_points(uint8_t *mark, int64_t n
 
 using namespace sgn;
 
+// The launches' grid caps.  tests/test_adam_gpu.py sizes its wrap cases by them: N_PASS = ADAM_GRID x 256
+// threads x 2 float4 x 4 elements of k_adam, CLAIM_PASS = CLAIM_GRID x CLAIM_PER entries of k_rows_claim,
+// UPDATE_PASS = UPDATE_GRID x 256 (row, element) pairs of k_rows_update, and its replays by kSchedWin.
+constexpr int ADAM_GRID = 256 * 16;
+constexpr int CLAIM_GRID = 256 * 4;
+constexpr int UPDATE_GRID = 256 * 64;
+
 extern "C" {
 
 int sgn_adam_step_multi(int32_t n_t, float *const *d_param, float *const *d_grad, float *const *d_exp_avg,
@@ -852,7 +859,7 @@ int sgn_adam_step_multi(int32_t n_t, float *const *d_param, float *const *d_grad
     a.eps = (float)eps;
     a.zero_grad = zero_grad ? 1 : 0;
     const int64_t n4 = a.off4[n_t];
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((n4 + 511) / 512, 256 * 16));
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((n4 + 511) / 512, ADAM_GRID));
     hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
@@ -933,10 +940,10 @@ int sgn_adam_rows(int32_t n_t, float *const *d_param, float *const *d_grad, floa
     hipStream_t st = as_stream(stream);
     SGN_CHECK_HIP(hipMemsetAsync(d_ws, 0, 4, st));
     if (d_pend) SGN_CHECK_HIP(hipMemsetAsync(d_pend, 0, 16, st));
-    const int64_t cblocks = std::max<int64_t>(1, std::min<int64_t>((entries + CLAIM_PER - 1) / CLAIM_PER, 256 * 4));
+    const int64_t cblocks = std::max<int64_t>(1, std::min<int64_t>((entries + CLAIM_PER - 1) / CLAIM_PER, CLAIM_GRID));
     hipLaunchKernelGGL(k_rows_claim, dim3((unsigned)cblocks), dim3(256), 0, st, a);
     SGN_CHECK_HIP(hipGetLastError());
-    const int64_t ublocks = std::max<int64_t>(1, std::min<int64_t>((a.cap * a.wsum + 255) / 256, 256 * 64));
+    const int64_t ublocks = std::max<int64_t>(1, std::min<int64_t>((a.cap * a.wsum + 255) / 256, UPDATE_GRID));
     hipLaunchKernelGGL(k_rows_update, dim3((unsigned)ublocks), dim3(256), 0, st, a);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
