@@ -280,6 +280,28 @@ int sgn_aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bp
 size_t sgn_aggregate_flag_offset_f32(size_t workspace_bytes);
 int64_t sgn_aggregate_fs_offset_f32(size_t workspace_bytes, int64_t S_capacity);
 
+/* The viewmlp without block3 (shading_feature_mlp_layer3 = 0; see sgn_aggregate_exact_nb3 below for the
+ * network) on the same split-fp16 kernels, its row layers fused in one kernel (ABI 23, additions): the row
+ * kernel's transposed last layer is block1.2, or block2_bpnet.0 with bpnet_layers = 1, and z1 / z2 never reach
+ * memory.  The projection, pairing and colour kernels are the stock ones.
+ *   sgn_mlp_packed_bytes_f32_nb3 : bytes of the blob (0 for an unsupported variant)
+ *   sgn_mlp_pack_f32_nb3         : the weights in sgn_mlp_pack_exact_nb3's order (block1.0, block1.2,
+ *                                  alpha_branch.0, color_branch.0, .2, .4, .6, + block2_bpnet.0 as 7)
+ *   sgn_point_project_f32_nb3    : sgn_point_project_f32 on that blob; pt->color and pt->dir are not read
+ *                                  and may be NULL
+ *   sgn_aggregate_f32_nb3        : sgn_aggregate_f32's arguments, stages, workspace layout, chunking and range
+ *                                  flag (sgn_aggregate_flag_offset_f32), on that blob and its projection;
+ *                                  pt->color and pt->dir are not read; pt->pers and pt->rot are refused */
+size_t sgn_mlp_packed_bytes_f32_nb3(int32_t bpnet_layers, int32_t bpnet_dim);
+int sgn_mlp_pack_f32_nb3(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
+                         void *d_packed, sgn_stream_t stream);
+int sgn_point_project_f32_nb3(const sgn_point_tables *pt, const void *d_packed_mlp, const int32_t *d_idx,
+                              const int64_t *d_count, void *d_proj, sgn_stream_t stream);
+int sgn_aggregate_f32_nb3(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const void *d_point_proj,
+                          const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
+                          const void *d_packed_mlp, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
+                          void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream);
+
 /* fp32-faithful training forward (SURVEY §8 f1 at the reference's arithmetic): stage 1 of
  * sgn_aggregate_f32 that also writes the pre-activations of block1.0 (d_z1), block1.2 (d_z2) and
  * block3.0 (d_z3) (2^-s (W x + b), before LeakyReLU) as fp32 [S_capacity * K][256] at row s * K + k

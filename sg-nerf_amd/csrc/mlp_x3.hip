@@ -205,6 +205,20 @@ struct NetR16SGT {
     static constexpr XL L[NL] = {{2, 16, 1, KC, OFF16_W0B}, {8, 16, 1, KC, OFF16_W1}, {KB, 16, 1, KC, OFF16_WB},
                                  {9, 16, 1, KC, OFF16_W2}, {8, 8, 2, 2 * KC, OFF16_W3}};
 };
+// The viewmlp without block3 (shading_feature_mlp_layer3 = 0): the last row layer -- block1.2, or
+// block2_bpnet.0 with its BPNet k-steps -- is the transposed one, in two passes of 8 output tiles
+// (sgn_mlp_pack_f32_nb3 packs it that way into the stock layer's section)
+struct NetR16N {
+    static constexpr int NW = NetR16T::NW, SP = NetR16T::SP, KC = NetR16T::KC;
+    static constexpr int NL = 2;
+    static constexpr XL L[NL] = {{2, 16, 1, KC, OFF16_W0B}, {8, 8, 2, 2 * KC, OFF16_W1}};
+};
+template <int KB>
+struct NetR16NSG {
+    static constexpr int NW = NetR16T::NW, SP = NetR16T::SP, KC = NetR16T::KC;
+    static constexpr int NL = 3;
+    static constexpr XL L[NL] = {{2, 16, 1, KC, OFF16_W0B}, {8, 16, 1, KC, OFF16_W1}, {KB, 8, 2, 2 * KC, OFF16_WB}};
+};
 struct NetProj16 {
     static constexpr int NW = NW16, SP = 32;  // 64-KiB ring slots
     static constexpr int NL = 1;
@@ -780,10 +794,16 @@ __device__ __forceinline__ Tiles grid_tiles(int ntiles) { return Tiles{(int)bloc
 // six MFMAs (half the LDS reads and weight DMA per MFMA of NS = 1), one workgroup per CU and one
 // wave per SIMD (the accumulators of two layers, 256 registers, sit in AGPRs)
 // ROT: rotated neural points (Rec16, row_math16 and the block3 extras below)
-template <int KB, bool PERS, bool SAVE = false, int NS = 1, bool ROT = false>
+// B3 = false: the viewmlp without block3 (NetR16N / NetR16NSG).  block3.0, its extras and block3.2 are
+// not instantiated; the transposed two-pass layer and the epilogue that hangs off it are block1.2
+// (base) or block2_bpnet.0 (SG, BPNet fragments as k-steps 8 .. 10), on a blob that holds that layer's
+// scaled bias, alpha weights and scale where the stock blob holds block3.2's.  Inference only.
+template <int KB, bool PERS, bool SAVE = false, int NS = 1, bool ROT = false, bool B3 = true>
 __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs a) {
-    using Net = std::conditional_t<(KB > 0), NetR16SGT<KB>, NetR16T>;
-    constexpr int LB = 2, L2 = KB ? 3 : 2, L3 = KB ? 4 : 3;
+    static_assert(B3 || (!SAVE && !ROT && !PERS), "without block3: the plain inference rows only");
+    using Net = std::conditional_t<B3, std::conditional_t<(KB > 0), NetR16SGT<KB>, NetR16T>,
+                                   std::conditional_t<(KB > 0), NetR16NSG<KB>, NetR16N>>;
+    constexpr int LB = 2, L2 = KB ? 3 : 2, L3 = B3 ? (KB ? 4 : 3) : (KB ? 2 : 1);
     constexpr int NBP = KB > 8 ? KB - 8 : 0;  // BPNet k-steps (32 channels each)
     constexpr int WGS = WG16_SAMPLES * NS;    // halves per workgroup tile
     __shared__ __attribute__((aligned(16))) char lds[ROWS16_LDS];
@@ -951,7 +971,7 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
                 if (a.blend && g == 0) a.blend[v] = rw[q].wgt;
                 if (a.wnorm && g == 1) a.wnorm[v] = rw[q].wn;
             }
-            {   // block3 extra channels: colour, dir - v, <dir, v> (:639-652), lane group 0
+            if constexpr (B3) {  // block3 extra channels: colour, dir - v, <dir, v> (:639-652), lane group 0
                 const bool e = g == 0 && m;
                 float u[8], pd[3] = {rc.dir[0], rc.dir[1], rc.dir[2]};
                 if constexpr (ROT) rot3(rc.R, pd[0], pd[1], pd[2], pd[0], pd[1], pd[2]);  // R_p dir_p
@@ -986,6 +1006,22 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
 #pragma unroll
             for (int t = 0; t < 16; ++t) ac[t] = *(const f32x4 *)(Yl + yb + 16 * t + 4 * g);
         };
+        // the next tile's row-table entries, then its neighbour / ray indices
+        int v_next[NS];
+        auto next_rows = [&]() {
+#pragma unroll
+            for (int q = 0; q < NS; ++q) v_next[q] = nslot[q] < nslots ? a.rows[(int64_t)nslot[q] * 8 + kk] : -1;
+        };
+        auto next_index = [&]() {
+#pragma unroll
+            for (int q = 0; q < NS; ++q) {
+                nx[q].sval = v_next[q] >= 0;
+                nx[q].s = nx[q].sval ? v_next[q] >> 3 : 0;
+                nx[q].a = (v_next[q] & 7) == kk;
+                nx[q].pid = nx[q].sval ? a.pidx[pidx_of(a, v_next[q])] : -1;
+                nx[q].ray = nx[q].sval ? a.samp_ray[nx[q].s] : 0;
+            }
+        };
         {   // block1.0: W0b PE(dists) on MFMA, + P[pid] (W0a [feat | PE(feat)] + b0, k_point_proj16)
             PeRow pr[NS];
 #pragma unroll
@@ -1002,25 +1038,41 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
 #pragma unroll
                     for (int q = 0; q < NS; ++q) o.b[q] = pe_dists16_k<decltype(k)::value>(pr[q]);
                     return o;
-                }, NoHook{});
+                }, [&](auto c) {  // without block3 the prefetch chain starts here: two layers carry it
+                    if constexpr (!B3 && decltype(c)::value == 0) next_rows();
+                    if constexpr (!B3 && decltype(c)::value == 1) next_index();
+                });
         }
         // block1.2: 256 -> 256 (input: block1.0 accumulators)
         const float inv0 = Yl[Y_INV + 0], inv1 = Yl[Y_INV + 1], inv2 = Yl[Y_INV + 2], inv7 = Yl[Y_INV + 7];
+        // without block3: the BPNet fragments of block2_bpnet.0's k-steps 8 .., gathered and split here, once
+        // per tile (block1.2's first boundary waits vmcnt(0), so the loads are waited for there, not hidden)
+        X3Pair bpn[NS][!B3 && NBP > 0 ? NBP : 1];
+        if constexpr (!B3 && NBP > 0) {
 #pragma unroll
-        for (int q = 0; q < NS; ++q) bias_init(accB[q], Y_B1);
-        int v_next[NS];
-        run_layer_ns<Net, 1, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, accB, [&](auto k) {
-            X3S<NS> o;
+            for (int q = 0; q < NS; ++q) {
+                const float *src = a.bpnet32 + (int64_t)(ix[q].pid >= 0 ? ix[q].pid : 0) * (NBP * 32) + 8 * g;
 #pragma unroll
-            for (int q = 0; q < NS; ++q) o.b[q] = chain_k(q, accA[q], inv0, k, a.z1);
-            return o;
-        }, [&](auto c) {
-            if constexpr (decltype(c)::value == 0) {
-#pragma unroll
-                for (int q = 0; q < NS; ++q) v_next[q] = nslot[q] < nslots ? a.rows[(int64_t)nslot[q] * 8 + kk] : -1;
+                for (int j = 0; j < NBP; ++j) {
+                    const f32x4 u0 = *(const f32x4 *)(src + 32 * j), u1 = *(const f32x4 *)(src + 32 * j + 4);
+                    const float v[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
+                    bpn[q][j] = split8_unit(v);
+                }
             }
-        });
-        if constexpr (KB > 0) {
+        }
+        if constexpr (B3 || KB > 0) {
+#pragma unroll
+            for (int q = 0; q < NS; ++q) bias_init(accB[q], Y_B1);
+            run_layer_ns<Net, 1, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, accB, [&](auto k) {
+                X3S<NS> o;
+#pragma unroll
+                for (int q = 0; q < NS; ++q) o.b[q] = chain_k(q, accA[q], inv0, k, a.z1);
+                return o;
+            }, [&](auto c) {
+                if constexpr (B3 && decltype(c)::value == 0) next_rows();
+            });
+        }
+        if constexpr (B3 && KB > 0) {
             // block2_bpnet.0 (SG): [h 256 | BPNet embedding] -> 256; the row's fp32 embedding
             // (channels 32 m + 8 g .. +7 for k-step 8 + m) gathered and split here
             X3Pair bpv[NS][NBP > 0 ? NBP : 1];
@@ -1053,32 +1105,27 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
         auto &in2 = pick<(KB > 0)>(accA, accB);
         auto &acc2 = pick<(KB > 0)>(accB, accA);
         const float inv_in2 = KB > 0 ? inv7 : inv1;
+        if constexpr (B3) {
 #pragma unroll
-        for (int q = 0; q < NS; ++q) bias_init(acc2[q], Y_B2);
-        run_layer_ns<Net, L2, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, acc2, [&](auto k) {
-            constexpr int K = decltype(k)::value;
-            X3S<NS> o;
-#pragma unroll
-            for (int q = 0; q < NS; ++q) {
-                if constexpr (K < 8) o.b[q] = chain_k(q, in2[q], inv_in2, k, KB > 0 ? a.zb : a.z2);
-                else o.b[q] = ext[q];
-            }
-            return o;
-        }, [&](auto c) {
-            constexpr int C = decltype(c)::value;
-            if constexpr (C == 0) {  // v_next landed at the previous boundaries
+            for (int q = 0; q < NS; ++q) bias_init(acc2[q], Y_B2);
+            run_layer_ns<Net, L2, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, acc2, [&](auto k) {
+                constexpr int K = decltype(k)::value;
+                X3S<NS> o;
 #pragma unroll
                 for (int q = 0; q < NS; ++q) {
-                    nx[q].sval = v_next[q] >= 0;
-                    nx[q].s = nx[q].sval ? v_next[q] >> 3 : 0;
-                    nx[q].a = (v_next[q] & 7) == kk;
-                    nx[q].pid = nx[q].sval ? a.pidx[pidx_of(a, v_next[q])] : -1;
-                    nx[q].ray = nx[q].sval ? a.samp_ray[nx[q].s] : 0;
+                    if constexpr (K < 8) o.b[q] = chain_k(q, in2[q], inv_in2, k, KB > 0 ? a.zb : a.z2);
+                    else o.b[q] = ext[q];
                 }
-            }
-        });
+                return o;
+            }, [&](auto c) {
+                if constexpr (decltype(c)::value == 0) next_index();  // v_next landed at the previous boundaries
+            });
+        }
         // block3.2: 256 -> 256 transposed: acc[t][i] = h[row 4 g + i][unit 16 t + (l & 15)]
+        // (without block3 the same holds one layer earlier: acc2 is block1.0's or block1.2's output, the
+        // input of the transposed block1.2 or block2_bpnet.0, and in2 is free for its accumulators)
         auto &acc = in2;  // block3.0's input is dead: its registers take block3.2's accumulators
+        const float inv_t = B3 ? inv2 : KB > 0 ? inv1 : inv0;  // 2^-s of the transposed layer's input
         {   // the accumulators start at 2^s3 b3 of the lane's units 16 t + r (the transposed LDS copy)
             const f32x4 *yb = (const f32x4 *)(ldsi + YT16_OFF + r * 80);
 #pragma unroll
@@ -1115,27 +1162,40 @@ __global__ __launch_bounds__(TPBR, NS == 1 ? 8 / NWR : 1) void k_rows16(AggArgs 
             // registers it frees) and pass 1 (tiles 8..15) reuses them; pass 1 carries the epilogue of
             // pass 0's tiles, output tile T after k-step T (one per 8 MFMA pairs)
             X3Pair in3[NS][8];
-            run_layer_ns<Net, L3, true, std::conditional_t<SAVE, VmZero, VmL3P0<NS>>, 0, 0, !SAVE>(
+            // (without block3 the record loads go out at the first boundary instead and every boundary waits
+            // vmcnt(0): the kernel reads fewer of the record's words, so REC16_LOADS is no lower bound there)
+            run_layer_ns<Net, L3, true, std::conditional_t<SAVE || !B3, VmZero, VmL3P0<NS>>, 0, 0, !SAVE>(
                 wb, ldsi, slot, w, lane, acc, [&](auto k) {
                     constexpr int K = decltype(k)::value;
                     X3S<NS> o;
 #pragma unroll
                     for (int q = 0; q < NS; ++q) {
-                        in3[q][K] = chain_k(q, acc2[q], inv2, k, a.z3);
-                        o.b[q] = in3[q][K];
+                        if constexpr (K < 8) {
+                            in3[q][K] = chain_k(q, acc2[q], inv_t, k, a.z3);
+                            o.b[q] = in3[q][K];
+                        } else {
+                            o.b[q] = bpn[q][K - 8];
+                        }
                     }
                     return o;
-                }, NoHook{}, first_chunk_loads);
+                }, [&](auto c) {
+                    if constexpr (!B3) first_chunk_loads(c);
+                }, [&](auto c) {
+                    if constexpr (B3) first_chunk_loads(c);
+                });
 #pragma unroll
             for (int q = 0; q < NS; ++q) epi_begin(e[q], ldsi, rw[q].wgt, nA[q], nB[q], ce[q], eslot[q] < nslots);
             run_layer_ns<Net, L3, true, VmZero, 1, 8>(wb, ldsi, slot, w, lane, acc, [&](auto k) {
                 X3S<NS> o;
 #pragma unroll
-                for (int q = 0; q < NS; ++q) o.b[q] = in3[q][decltype(k)::value];
+                for (int q = 0; q < NS; ++q) {
+                    if constexpr (decltype(k)::value < 8) o.b[q] = in3[q][decltype(k)::value];
+                    else o.b[q] = bpn[q][decltype(k)::value - 8];
+                }
                 return o;
             }, NoHook{}, NoHook{}, [&](auto f) {
                 constexpr int F = decltype(f)::value;
-                if constexpr ((F & 7) == 7) {
+                if constexpr ((F & 7) == 7 && F < 64) {  // (block2_bpnet.0's BPNet k-steps carry none)
 #pragma unroll
                     for (int q = 0; q < NS; ++q) epi_step(e[q], ldsi, acc[q], std::integral_constant<int, F / 8>{});
                 }
@@ -1527,6 +1587,48 @@ void pack_blob_x3(int ksb, int bpnet_dim, const float *const *w, const float *co
     pack_blob16(ksb, bpnet_dim, w, b, s, sb, blob);
 }
 
+// The viewmlp without block3 (k_rows16<.., B3 = false>), into the stock layout: w[] / b[] in the order of
+// sgn_mlp_pack_exact_nb3 -- block1.0, block1.2, alpha_branch.0, color_branch.0, .2, .4, .6 (+ block2_bpnet.0 as
+// 7).  The last row layer (block1.2, or block2_bpnet.0) goes into its stock section in two passes of 8 output
+// tiles; its scaled bias, the alpha weights over its scale and that scale take block3.2's places (Y_B3, Y_WA,
+// Y_INV + 3: what the transposed LDS copy and the epilogue read).  block3's sections, and Y_B1 of the base
+// network, stay zero; the projection and colour sections are the stock ones, so k_point_proj16 and k_color16
+// run on this blob as they are.
+void pack_blob_nb3(int ksb, int bpnet_dim, const float *const *w, const float *const *b, uint8_t *blob) {
+    const int nin_b = 256 + bpnet_dim;
+    const int s0 = layer_shift(w[0], 256 * 284), s1 = layer_shift(w[1], 256 * 256);
+    const int sc[3] = {layer_shift(w[3], 128 * 280), layer_shift(w[4], 128 * 128), layer_shift(w[5], 128 * 128)};
+    const int sb = ksb > 0 ? layer_shift(w[7], (size_t)256 * nin_b) : 0;
+    const int last = ksb > 0 ? 7 : 1, sl = ksb > 0 ? sb : s1;
+    auto frag = [&](uint32_t off) { return (_Float16 *)(blob + off); };
+    pack_pairs16(frag(OFF16_W0B), w[0], 256, 284, 2, s0, col_l0b16);
+    pack_pairs16(frag(OFF16_W0A), w[0], 256, 284, 7, s0, col_proj16);
+    pack_pairs16(frag(OFF16_W1), w[1], 256, 256, 8, s1, col_chain16, 16, ksb > 0 ? 1 : 2);
+    if (ksb > 0) pack_pairs16(frag(OFF16_WB), w[7], 256, nin_b, 8 + bpnet_dim / 32, sb, col_bp16, 16, 2);
+    pack_pairs16(frag(OFF16_C0), w[3], 128, 280, 9, sc[0], col_c016, 8);
+    pack_pairs16(frag(OFF16_C1), w[4], 128, 128, 4, sc[1], col_chain16, 8);
+    pack_pairs16(frag(OFF16_C2), w[5], 128, 128, 4, sc[2], col_chain16, 8);
+    float *Y = (float *)(blob + OFF16_F32);
+    for (int u = 0; u < HID; ++u) {
+        Y[Y_B0 + u] = b[0][u] * ldexpf(1.f, s0);
+        if (ksb > 0) Y[Y_B1 + u] = b[1][u] * ldexpf(1.f, s1);
+        Y[Y_B3 + u] = b[last][u] * ldexpf(1.f, sl);
+        Y[Y_WA + u] = w[2][u] * ldexpf(1.f, -sl);
+    }
+    Y[Y_BA] = b[2][0];
+    Y[Y_INV + 0] = ldexpf(1.f, -s0);
+    Y[Y_INV + 1] = ldexpf(1.f, -s1);
+    Y[Y_INV + 3] = ldexpf(1.f, -sl);
+    for (int i = 0; i < 3; ++i) Y[Y_INV + 4 + i] = ldexpf(1.f, -sc[i]);
+    for (int u = 0; u < 128; ++u) {
+        Y[Y_CB0 + u] = b[3][u] * ldexpf(1.f, sc[0]);
+        Y[Y_CB1 + u] = b[4][u] * ldexpf(1.f, sc[1]);
+        Y[Y_CB2 + u] = b[5][u] * ldexpf(1.f, sc[2]);
+        for (int c = 0; c < 3; ++c) Y[Y_CW3 + 128 * c + u] = w[6][c * 128 + u];
+    }
+    for (int c = 0; c < 3; ++c) Y[Y_CB3 + c] = b[6][c];
+}
+
 }  // namespace x3
 }  // namespace
 }  // namespace sgn
@@ -1564,24 +1666,62 @@ int sgn_mlp_pack_f32_host(int32_t bpnet_layers, int32_t bpnet_dim, const float *
     return 0;
 }
 
-int sgn_point_project_f32(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
-                          const int64_t *d_count, void *d_proj, sgn_stream_t stream) {
+}  // extern "C"
+
+// B3 = false (sgn_point_project_f32_nb3): pt->color and pt->dir are not read -- the record's colour and dir
+// words, which k_rows16 without block3 never reads, are filled from xyz, so k_point_proj16 runs as it is
+template <bool B3>
+static int point_project_f32(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
+                             const int64_t *d_count, void *d_proj, sgn_stream_t stream) {
     using namespace sgn;
     SGN_REQUIRE(pt && d_packed && d_proj, "null argument");
     SGN_REQUIRE((d_idx == nullptr) == (d_count == nullptr), "d_idx and d_count go together (both null: every point)");
     SGN_REQUIRE(pt->n_points >= 0 && (pt->n_points == 0 || pt->embedding), "embedding required");
     SGN_REQUIRE(((uintptr_t)d_proj & 15) == 0 && ((uintptr_t)pt->embedding & 15) == 0, "16-byte alignment required");
     if (pt->n_points == 0) return 0;
-    SGN_REQUIRE(pt->xyz && pt->color && pt->dir && pt->conf, "point tables (xyz, color, dir, conf) required");
+    if (B3) SGN_REQUIRE(pt->xyz && pt->color && pt->dir && pt->conf, "point tables (xyz, color, dir, conf) required");
+    else SGN_REQUIRE(pt->xyz && pt->conf, "point tables (xyz, conf) required");
     float *rec = (float *)((char *)d_proj + (size_t)pt->n_points * x3::PROJ_BYTES_PER_POINT);
-    x3::Proj16Args a{pt->embedding, pt->n_points, d_packed, (float *)d_proj, pt->xyz, pt->color, pt->dir,
-                     pt->conf, rec, d_idx, d_count};
+    x3::Proj16Args a{pt->embedding, pt->n_points, d_packed, (float *)d_proj, pt->xyz, B3 ? pt->color : pt->xyz,
+                     B3 ? pt->dir : pt->xyz, pt->conf, rec, d_idx, d_count};
     // persistent grid: with a list it runs over the device count (a training step touches ~50 k of 1.2 M points)
     const int64_t tiles = (pt->n_points + 16 * x3::NW16 - 1) / (16 * x3::NW16);
     hipLaunchKernelGGL(x3::k_point_proj16, dim3((unsigned)(tiles < 256 ? tiles : 256)), dim3(x3::TPB16), 0,
                        as_stream(stream), a);
     SGN_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" {
+
+int sgn_point_project_f32(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
+                          const int64_t *d_count, void *d_proj, sgn_stream_t stream) {
+    return point_project_f32<true>(pt, d_packed, d_idx, d_count, d_proj, stream);
+}
+
+// ---- the viewmlp without block3 on the same kernels (k_rows16<.., B3 = false>) ----
+size_t sgn_mlp_packed_bytes_f32_nb3(int32_t bpnet_layers, int32_t bpnet_dim) {
+    return sgn_mlp_packed_bytes_f32(bpnet_layers, bpnet_dim);
+}
+
+int sgn_mlp_pack_f32_nb3(int32_t bpnet_layers, int32_t bpnet_dim, const float *const *w, const float *const *b,
+                         void *d_packed, sgn_stream_t stream) {
+    using namespace sgn;
+    SGN_REQUIRE(w && b && d_packed, "null argument");
+    const int ksb = mlp::variant_ksb(bpnet_layers, bpnet_dim);
+    SGN_REQUIRE_VARIANT(ksb);
+    for (int L = 0; L < (ksb ? 8 : 7); ++L) SGN_REQUIRE(w[L] && b[L], "null layer pointer");
+    std::vector<uint8_t> blob(x3::blob_bytes_sg(ksb), 0);
+    x3::pack_blob_nb3(ksb, bpnet_dim, w, b, blob.data());
+    hipStream_t st = as_stream(stream);
+    SGN_CHECK_HIP(hipMemcpyAsync(d_packed, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    SGN_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int sgn_point_project_f32_nb3(const sgn_point_tables *pt, const void *d_packed, const int32_t *d_idx,
+                              const int64_t *d_count, void *d_proj, sgn_stream_t stream) {
+    return point_project_f32<false>(pt, d_packed, d_idx, d_count, d_proj, stream);
 }
 
 size_t sgn_point_proj_bytes_f32(int64_t n_points) {
@@ -1623,11 +1763,16 @@ auto rows_kernel(int ksb, bool rot = false) {
                                                                             : x3::k_rows16<11, PERS, SAVE, NS>;
 }
 
+// the viewmlp without block3 (sgn_aggregate_f32_nb3), defined after aggregate_f32: its instantiations are then
+// emitted after the stock kernels, which keep the code addresses they had before these existed
+void (*rows_kernel_nb3(int ksb, int &ns))(sgn::AggArgs);
+
+// nb3: the viewmlp without block3, on a blob of sgn_mlp_pack_f32_nb3
 int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const void *d_point_proj,
                   const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
                   const void *d_packed, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
                   void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream,
-                  float *const *z = nullptr, const int32_t *row_off = nullptr) {
+                  float *const *z = nullptr, const int32_t *row_off = nullptr, bool nb3 = false) {
     using namespace sgn;
     using namespace sgn::mlp;
     SGN_REQUIRE(pt && q && d_packed && d_out_feat && d_workspace && d_point_proj, "null argument");
@@ -1638,6 +1783,11 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
                 "bpnet_dim > 0 needs the 16-byte aligned fp32 BPNet point embedding");
     SGN_REQUIRE(K >= 1 && K <= 8, "the fp32 MFMA aggregator takes K = 1 .. 8 neighbours per sample");
     SGN_REQUIRE(pt->campos && pt->camrotc2w && pt->raydir, "camera (campos, camrotc2w, raydir) required");
+    if (nb3) {
+        SGN_REQUIRE(!pt->pers && !pt->samp_pers,
+                    "pers (the caller's pers coordinates) is not supported by the fused rows without block3");
+        SGN_REQUIRE(!pt->rot, "rot (per-point Rw2c) is not supported by the fused rows without block3");
+    }
     SGN_REQUIRE((pt->pers == nullptr) == (pt->samp_pers == nullptr), "pers and samp_pers go together");
     SGN_REQUIRE_ROT(pt, ksb);
     SGN_REQUIRE(!(pt->rot && z), "rot (per-point Rw2c) is not supported by the training forward");
@@ -1698,8 +1848,9 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
                                pair, rows, slots, slot_n);
             // inference rows: 32 rows per wave (NS = 2; 0.94x the time of NS = 1 at config 2,
             // profiles/r04_v2_bench_rows_ns*.json); the save mode (training) keeps NS = 1
-            const int ns = z ? 1 : 2;
-            auto kern = z ? rows_kernel<false, true, 1>(ksb)              // <PERS, SAVE, NS>
+            int ns = z ? 1 : 2;
+            auto kern = nb3 ? rows_kernel_nb3(ksb, ns)
+                        : z ? rows_kernel<false, true, 1>(ksb)            // <PERS, SAVE, NS>
                           : pt->pers ? rows_kernel<true, false, 2>(ksb)  // the caller's pers coordinates
                                      : rows_kernel<false, false, 2>(ksb, pt->rot != nullptr);
             const int64_t wg16 = (n + x3::WG16_SAMPLES * ns - 1) / (x3::WG16_SAMPLES * ns),
@@ -1715,6 +1866,16 @@ int aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,
     return 0;
 }
 
+// The plain inference rows.  NS = 2, except block2_bpnet.0 on 256 inputs: at NS = 2 that instantiation spills (88 B
+// of scratch per lane), at NS = 1 it does not
+void (*rows_kernel_nb3(int ksb, int &ns))(sgn::AggArgs) {
+    using namespace sgn;
+    ns = ksb == mlp::KS_HID ? 1 : 2;
+    return ksb == 0 ? x3::k_rows16<0, false, false, 2, false, false>
+                    : ksb == mlp::KS_HID ? x3::k_rows16<8, false, false, 1, false, false>
+                                         : x3::k_rows16<11, false, false, 2, false, false>;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1725,6 +1886,14 @@ int sgn_aggregate_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bp
                       void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream) {
     return aggregate_f32(bpnet_layers, bpnet_dim, d_bpnet, d_point_proj, pt, q, S_capacity, K, d_packed, d_out_feat,
                          d_out_blend, d_out_wnorm, d_workspace, workspace_bytes, stages, stream);
+}
+
+int sgn_aggregate_f32_nb3(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet, const void *d_point_proj,
+                          const sgn_point_tables *pt, const sgn_query_out *q, int64_t S_capacity, int32_t K,
+                          const void *d_packed, float *d_out_feat, float *d_out_blend, float *d_out_wnorm,
+                          void *d_workspace, size_t workspace_bytes, int32_t stages, sgn_stream_t stream) {
+    return aggregate_f32(bpnet_layers, bpnet_dim, d_bpnet, d_point_proj, pt, q, S_capacity, K, d_packed, d_out_feat,
+                         d_out_blend, d_out_wnorm, d_workspace, workspace_bytes, stages, stream, nullptr, nullptr, true);
 }
 
 int sgn_aggregate_train_fwd_f32(int32_t bpnet_layers, int32_t bpnet_dim, const float *d_bpnet,

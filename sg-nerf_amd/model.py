@@ -79,6 +79,9 @@ class HipPointsVolumetricModel:
         parser.add_argument("--sgn_rows_gemm", type=int, default=0,
                             help="1: render the viewmlp without block3 (shading_feature_mlp_layer3 = 0) on the "
                                  "split-fp16 row GEMMs instead of the plain-fp32 kernels")
+        parser.add_argument("--sgn_rows_fused", type=int, default=0,
+                            help="1: render the viewmlp without block3 (shading_feature_mlp_layer3 = 0) on the "
+                                 "fused split-fp16 row kernel instead of the plain-fp32 kernels")
         parser.add_argument("--sgn_train_rows", type=int, default=0,
                             help="1: train the viewmlp without block3 (shading_feature_mlp_layer3 = 0) with the fp32 "
                                  "step on the split-fp16 row GEMMs; 0: training that network is refused")
@@ -111,6 +114,8 @@ class HipPointsVolumetricModel:
             extra["early_stop_slots"] = tuple(int(x) for x in str(opt.sgn_early_stop_slots).replace(",", " ").split())
         if getattr(opt, "sgn_rows_gemm", 0):   # or rows_gemm itself in the namespace (from_opt)
             extra["rows_gemm"] = int(opt.sgn_rows_gemm)
+        if getattr(opt, "sgn_rows_fused", 0):  # or rows_fused itself in the namespace (from_opt)
+            extra["rows_fused"] = int(opt.sgn_rows_fused)
         if getattr(opt, "sgn_train_rows", 0):  # or train_rows itself in the namespace (from_opt)
             extra["train_rows"] = int(opt.sgn_train_rows)
         # rendering (test / probe) runs the test-mode depth table; the trainer jitters (is_train)
@@ -240,10 +245,10 @@ class HipPointsVolumetricModel:
         # the step at the model's arithmetic: precision "f32" (the reference's) trains through the
         # fp32-faithful forward and the fp32 backward (base viewmlp and SG's block2_bpnet alike)
         prec = "f16" if self.opts.precision == "f16" else "f32"
-        # the rendering options stay as they are (test frames may render with rows_gemm = 1, which does not
+        # the rendering options stay as they are (test frames may render with rows_gemm = 1 or rows_fused = 1, which do not
         # combine with is_train); the trainer's are its own
         self.trainer = HipTrainer(params, self.net_ray_marching.renderer.mlp_state,
-                                  dataclasses.replace(self.opts, is_train=1, rows_gemm=0), self.device,
+                                  dataclasses.replace(self.opts, is_train=1, rows_gemm=0, rows_fused=0), self.device,
                                   lr=g("lr", 5e-4), plr=g("plr", 2e-3), lr_decay_exp=g("lr_decay_exp", 0.1),
                                   lr_decay_iters=g("lr_decay_iters", 1_000_000), bpnet=bp, precision=prec)
         # the renderer reads the trained tensors in place (views; the table cache follows their versions)

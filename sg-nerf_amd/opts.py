@@ -113,6 +113,9 @@ class HotPathOpts:
     # 1: HipRenderer renders the viewmlp without block3 (shading_feature_mlp_layer3 = 0) on the split-fp16 row
     # GEMMs (sgn_x3_gemm over item windows, render.py) instead of the plain-fp32 kernels.  0 = off.
     rows_gemm: int = 0
+    # 1: HipRenderer renders that network on the fused split-fp16 row kernel (k_rows16 without block3,
+    # sgn_aggregate_f32_nb3): the stock f32 path's frame with two of its row layers.  0 = off.
+    rows_fused: int = 0
     # 1: HipTrainer trains the viewmlp without block3 (shading_feature_mlp_layer3 = 0) with the fp32 step on the
     # split-fp16 row GEMMs (train_f32.F32StepNb3).  0 = off: training that network stays refused.
     train_rows: int = 0
@@ -231,7 +234,8 @@ class HotPathOpts:
                     if isinstance(v, str):
                         v = tuple(int(x) for x in v.replace(",", " ").split())
                     v = v if isinstance(v, tuple) else (int(v),)
-                if f.name in ("early_stop", "zero_epsilon", "sparse_loss_weight", "rows_gemm", "train_rows") and v is None:
+                if f.name in ("early_stop", "zero_epsilon", "sparse_loss_weight", "rows_gemm", "rows_fused",
+                              "train_rows") and v is None:
                     continue
                 kw[f.name] = v
         # argparse's lone default weight beside unset items (color_loss_items None, color_loss_weights [1.0]):
@@ -338,6 +342,18 @@ class HotPathOpts:
                 bad.append("rows_gemm = 1 is the split-fp16 fp32-faithful path: precision must be 'f32'")
             if self.is_train:
                 bad.append("rows_gemm = 1 renders only: not with is_train")
+        rf = self.rows_fused
+        if isinstance(rf, bool) or not isinstance(rf, numbers.Integral) or rf not in (0, 1):
+            bad.append("rows_fused must be 0 or 1")
+        elif rf == 1:
+            if self.shading_feature_mlp_layer3 != 0:
+                bad.append("rows_fused = 1 renders the viewmlp without block3 only (shading_feature_mlp_layer3 = 0)")
+            if self.precision != "f32":
+                bad.append("rows_fused = 1 is the split-fp16 fp32-faithful path: precision must be 'f32'")
+            if self.is_train:
+                bad.append("rows_fused = 1 renders only: not with is_train")
+            if not isinstance(rg, bool) and isinstance(rg, numbers.Integral) and rg == 1:
+                bad.append("rows_fused = 1 and rows_gemm = 1 are two paths for the same frames: set one of them")
         tr = self.train_rows
         if isinstance(tr, bool) or not isinstance(tr, numbers.Integral) or tr not in (0, 1):
             bad.append("train_rows must be 0 or 1")

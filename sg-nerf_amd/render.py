@@ -94,15 +94,24 @@ class PointTables:
 
 
 class HipRenderer:
-    def __init__(self, points: PointTables, mlp_state, opts: HotPathOpts, device, rows_gemm=None, rows_ci=None):
+    def __init__(self, points: PointTables, mlp_state, opts: HotPathOpts, device, rows_gemm=None, rows_ci=None,
+                 rows_fused=None):
         """rows_gemm (0 / 1): overrides opts.rows_gemm -- the viewmlp without block3 on the split-fp16 row GEMMs
-        (rows_gemm.RowsGemmNb3).  rows_ci: that path's window size in work items (default: CI K <= 1 M rows)."""
+        (rows_gemm.RowsGemmNb3).  rows_ci: that path's window size in work items (default: CI K <= 1 M rows).
+        rows_fused (0 / 1): overrides opts.rows_fused -- that network on the fused split-fp16 row kernel
+        (sgn_aggregate_f32_nb3)."""
         self.device = torch.device(device)
         if rows_gemm is not None:
             opts = replace(opts, rows_gemm=rows_gemm)
+        if rows_fused is not None:
+            opts = replace(opts, rows_fused=rows_fused)
         self.opts = opts.check_supported()
         if self.opts.rows_gemm and self.opts.K > 8:
             raise NotImplementedError(f"rows_gemm = 1 holds a sample's rows in one wave: K <= 8, not {self.opts.K}")
+        if self.opts.rows_fused and self.opts.K > 8:
+            raise NotImplementedError(f"rows_fused = 1 holds a sample's rows in one 8-row half: K <= 8, not {self.opts.K}")
+        self.fused = bool(self.opts.rows_fused)   # rows_fused = 1: the viewmlp without block3 on the fused row kernel
+        self._fused_frame = False                 # the last frame was aggregated on it
         self._rows_ci = rows_ci
         self.rows = None           # rows_gemm = 1: the row-GEMM path's weights, window buffers and launch arguments
         self._rows_frame = False   # the last frame was aggregated on it
@@ -139,6 +148,12 @@ class HipRenderer:
                 # ... or, opted in, on the split-fp16 row GEMMs, with the plain-fp32 path as the range fallback
                 # (`exact` turns on once a frame's activations left fp16 range) and for rotated points / tiers
                 self.rows = RowsGemmNb3(self.mlp_state, self.variant, self.opts.K, self._rows_ci, self.device)
+                self.exact = False
+            if self.fused:
+                # ... or on the fused split-fp16 row kernel: the stock f32 path's frame (frame point list,
+                # projection, paired rows, colour, workspace range flag) on its own blob, with the plain-fp32 path
+                # as the range fallback and for rotated points
+                self.packed = pack_mlp(self.mlp_state, self.device, "fused", block3_layers=0)
                 self.exact = False
             return
         self.packed = pack_mlp(self.mlp_state, self.device, self.opts.precision)
@@ -203,6 +218,8 @@ class HipRenderer:
             return
         if self.rows is not None and not self._rows_frame:
             return   # rows_gemm = 1, but this frame ran on the plain-fp32 path (rotated points, early-stop tiers)
+        if self.fused and not self._fused_frame:
+            return   # rows_fused = 1, but this frame ran on the plain-fp32 path (rotated points)
         if mode == "sync":
             flag = self._flag()
             if int(flag.item()) != 0:
@@ -237,7 +254,7 @@ class HipRenderer:
         entries zero blend / wnorm on every call, and the hole probe must see every sample), or the
         plain-fp32 range fallback."""
         o = self.opts
-        if not o.early_stop > 0 or o.is_train or want_probe or want_weights or want_blend or self.exact:
+        if not o.early_stop > 0 or o.is_train or want_probe or want_weights or want_blend or self.exact or o.rows_fused:
             return ()
         return o.early_stop_tiers
 
@@ -257,6 +274,9 @@ class HipRenderer:
         (semantic_guidance = 1, worldcoords.py:839-938).  `check_range`: the f32 mode's fp16-range
         guard ("sync" default: a frame whose activations leave fp16 range is re-rendered on the
         plain-fp32 path, sgn_aggregate_exact; "deferred" for pipelined frame loops + finish(), False).
+        The viewmlp without block3 with rows_fused = 1 takes the stock protocol as it is (the workspace flag of
+        sgn_aggregate_f32_nb3, fallback sgn_aggregate_exact_nb3) and renders frames of rotated points on the
+        plain-fp32 path and every frame in full (no early-stop tiers).
         The viewmlp without block3 with rows_gemm = 1 follows the same protocol on its own amax words
         (rows_gemm.RowsGemmNb3.flag, fallback sgn_aggregate_exact_nb3); that path reads the frame's item count
         on the host once per frame (one small copy and stream sync, whatever check_range says), and renders
@@ -343,11 +363,15 @@ class HipRenderer:
         # split block1.0: P[point] = W0a [feat | PE(feat)] + b0, once per frame, for the points the
         # frame's samples name only (sgn_frame_points: ~19 % of a config-2 frame's)
         mark("proj")
-        nproj = 0 if not self.block3 else int(L.sgn_point_proj_bytes_f32(self.points.n) if self.f32 else
-                                              L.sgn_point_proj_bytes(self.points.n))
-        if self.block3 and (self._proj is None or self._proj.numel() < nproj):
+        # rows_fused = 1: the frame on the fused row kernel, unless the plain-fp32 path has to take it (after a range
+        # fallback, with rotated points)
+        self._fused_frame = self.fused and not self.exact and self.points.rot is None
+        split = self.block3 or self.fused   # the paths that read a point projection
+        nproj = 0 if not split else int(L.sgn_point_proj_bytes_f32(self.points.n) if self.f32 else
+                                        L.sgn_point_proj_bytes(self.points.n))
+        if split and (self._proj is None or self._proj.numel() < nproj):
             self._proj = torch.empty(max(nproj, 16), dtype=torch.uint8, device=self.device)
-        if not self.exact and self.block3:
+        if not self.exact and (self.block3 or self._fused_frame):
             n = self.points.n
             if self._fp is None or self._fp[0] != n:
                 self._fp = (n, torch.zeros(int(L.sgn_frame_points_mark_bytes(n)), dtype=torch.uint8, device=self.device),
@@ -356,7 +380,8 @@ class HipRenderer:
             _, marks, plist, pcount = self._fp
             _lib.check(L.sgn_frame_points(_lib.ptr(q.pidx), _lib.ptr(q.counters), q.pidx.numel() // o.K, o.K, n,
                                           _lib.ptr(marks), _lib.ptr(plist), _lib.ptr(pcount), st), "sgn_frame_points")
-            project = L.sgn_point_project_f32 if self.f32 else L.sgn_point_project   # different arithmetic
+            project = (L.sgn_point_project_f32_nb3 if self.fused else
+                       L.sgn_point_project_f32 if self.f32 else L.sgn_point_project)   # different arithmetic
             _lib.check(project(ctypes.byref(pt), _lib.ptr(self.packed), _lib.ptr(plist), _lib.ptr(pcount),
                                _lib.ptr(self._proj), st), "point projection (frame list)")
         cp = _lib.CompositeParams()
@@ -369,7 +394,12 @@ class HipRenderer:
         def aggregate(stage, qa):
             blend = _lib.ptr(self.blend) if want_blend else None
             wnorm = _lib.ptr(self.wnorm) if want_weights and stage == 1 else None
-            if self.f32:
+            if self.fused:
+                _lib.check(L.sgn_aggregate_f32_nb3(nl, dim, bp, _lib.ptr(self._proj), ctypes.byref(pt), ctypes.byref(qa),
+                                                   cap, o.K, _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
+                                                   _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st),
+                           "sgn_aggregate_f32_nb3")
+            elif self.f32:
                 _lib.check(L.sgn_aggregate_f32(nl, dim, bp, _lib.ptr(self._proj), ctypes.byref(pt), ctypes.byref(qa), cap, o.K,
                                                _lib.ptr(self.packed), _lib.ptr(self.feat), blend, wnorm,
                                                _lib.ptr(self.agg_ws), self.agg_ws.numel(), stage, st), "sgn_aggregate_f32")
@@ -412,7 +442,7 @@ class HipRenderer:
                     if stage == 1:
                         self.rows.run(pt, qo, q, cap, bp, self.feat, self.blend if want_blend else None,
                                       self.wnorm if want_weights else None)
-                elif self.exact or self.rows is not None:
+                elif self.exact or self.rows is not None or (self.fused and not self._fused_frame):
                     if stage == 1:
                         aggregate_exact()
                 else:

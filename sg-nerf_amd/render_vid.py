@@ -81,9 +81,12 @@ def main(argv=None):
     ap.add_argument("--early_stop", type=float, default=0.0, help="early ray termination threshold (0 = off)")
     ap.add_argument("--mlp_layer3", type=int, default=2, choices=[0, 2],
                     help="shading_feature_mlp_layer3: 0 = the viewmlp without block3 (the SG-NeRF scripts' network; "
-                         "--precision f32 only; plain fp32, or the row GEMMs with --rows_gemm 1)")
+                         "--precision f32 only; plain fp32, the row GEMMs with --rows_gemm 1, or the fused row kernel with "
+                         "--rows_fused 1)")
     ap.add_argument("--rows_gemm", type=int, default=0, choices=[0, 1],
                     help="1: render --mlp_layer3 0 on the split-fp16 row GEMMs instead of the plain-fp32 kernels")
+    ap.add_argument("--rows_fused", type=int, default=0, choices=[0, 1],
+                    help="1: render --mlp_layer3 0 on the fused split-fp16 row kernel instead of the plain-fp32 kernels")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -93,7 +96,8 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group("nccl", device_id=dev)
     o = HotPathOpts(SR=args.sr, precision=args.precision, early_stop=args.early_stop,
-                    shading_feature_mlp_layer3=args.mlp_layer3, rows_gemm=args.rows_gemm)
+                    shading_feature_mlp_layer3=args.mlp_layer3, rows_gemm=args.rows_gemm,
+                    rows_fused=args.rows_fused)
     if args.checkpoint:
         from .ray_marching import NeuralPoints
         from .weights import block3_layers, strip_prefix

@@ -112,17 +112,20 @@ def pack_mlp(state, device, precision="f16", block3_layers=2):
     """fp32 state -> packed MFMA fragment blob on `device` (uint8 tensor).  precision "f16":
     fp16 fragments (mlp.hip); "f32": (hi, lo) fp16 fragment pairs of 2^s-scaled weights plus
     fp32 biases (mlp_x3.hip, the reference's fp32 arithmetic); "exact": plain fp32 W^T per layer
-    (exact.hip, the f32 mode's range fallback).  block3_layers = 0: the viewmlp without block3, "exact" only
-    (sgn_mlp_pack_exact_nb3)."""
+    (exact.hip, the f32 mode's range fallback).  block3_layers = 0: the viewmlp without block3, "exact"
+    (sgn_mlp_pack_exact_nb3) or "fused": the split-fp16 blob of the fused row kernel (sgn_mlp_pack_f32_nb3)."""
     state = strip_prefix(state, block3_layers=block3_layers)
     check_shapes(state, block3_layers)
     nl, dim = mlp_variant(state)
     layers = layers_for(nl, dim, block3_layers)
     L = _lib.lib()
-    if block3_layers == 0 and precision != "exact":
-        raise ValueError("the viewmlp without block3 (shading_feature_mlp_layer3 = 0) packs for the plain-fp32 "
-                         "kernels only: precision 'exact'")
-    nbytes = int(L.sgn_mlp_packed_bytes_exact_nb3(nl, dim) if block3_layers == 0 else
+    if block3_layers == 0 and precision not in ("exact", "fused"):
+        raise ValueError("the viewmlp without block3 (shading_feature_mlp_layer3 = 0) packs with precision 'exact' (the "
+                         f"plain-fp32 kernels) or 'fused' (the fused split-fp16 row kernel), not {precision!r}")
+    if block3_layers != 0 and precision == "fused":
+        raise ValueError("precision 'fused' packs the viewmlp without block3 only (block3_layers = 0)")
+    nbytes = int(L.sgn_mlp_packed_bytes_f32_nb3(nl, dim) if precision == "fused" else
+                 L.sgn_mlp_packed_bytes_exact_nb3(nl, dim) if block3_layers == 0 else
                  L.sgn_mlp_packed_bytes_f32(nl, dim) if precision == "f32" else
                  L.sgn_mlp_packed_bytes_exact(nl, dim) if precision == "exact" else L.sgn_mlp_packed_bytes(nl, dim))
     out = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -138,6 +141,9 @@ def pack_mlp(state, device, precision="f16", block3_layers=2):
     with torch.cuda.device(device):
         if precision == "f32":
             _lib.check(L.sgn_mlp_pack_f32(nl, dim, wp, bp, _lib.ptr(out), _lib.stream_handle()), "sgn_mlp_pack_f32")
+        elif precision == "fused":
+            _lib.check(L.sgn_mlp_pack_f32_nb3(nl, dim, wp, bp, _lib.ptr(out), _lib.stream_handle()),
+                       "sgn_mlp_pack_f32_nb3")
         elif block3_layers == 0:
             _lib.check(L.sgn_mlp_pack_exact_nb3(nl, dim, wp, bp, _lib.ptr(out), _lib.stream_handle()),
                        "sgn_mlp_pack_exact_nb3")

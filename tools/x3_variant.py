@@ -145,9 +145,9 @@ __device__ __forceinline__ void tst(bool on, int w, int it, int n) {
         tst(tdo, w, tit, 0);
         const int base = tile * WGS;''')
         for a, b in (("            run_layer_ns<Net, 0, false, std::conditional_t<SAVE, VmZero, VmL0<NS>>, 0, 0, !SAVE>(", 1),
-                     ("        run_layer_ns<Net, 1, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, accB, [&](auto k) {", 2),
-                     ("        run_layer_ns<Net, L2, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, acc2, [&](auto k) {", 3),
-                     ("            run_layer_ns<Net, L3, true, std::conditional_t<SAVE, VmZero, VmL3P0<NS>>, 0, 0, !SAVE>(", 4)):
+                     ("            run_layer_ns<Net, 1, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, accB, [&](auto k) {", 2),
+                     ("            run_layer_ns<Net, L2, false, VmZero, 0, 0, !SAVE>(wb, ldsi, slot, w, lane, acc2, [&](auto k) {", 3),
+                     ("            run_layer_ns<Net, L3, true, std::conditional_t<SAVE || !B3, VmZero, VmL3P0<NS>>, 0, 0, !SAVE>(", 4)):
             s = rep(s, a, " " * (len(a) - len(a.lstrip())) + f"tst(tdo, w, tit, {b});\n" + a)
         s = rep(s, "            run_layer_ns<Net, L3, true, VmZero, 1, 8>(wb, ldsi, slot, w, lane, acc, [&](auto k) {",
                 "            tst(tdo, w, tit, 5);\n            run_layer_ns<Net, L3, true, VmZero, 1, 8>(wb, ldsi, slot, w, lane, acc, [&](auto k) {")
@@ -271,40 +271,35 @@ __device__ __forceinline__ void dma_dup(const WBlob &wb, char *dst, int lane) {
         const float inv_in2 = KB > 0 ? inv7 : inv1;
         X3Pair in3[NS][8];
         constexpr int LASTK = (Net::L[L2].ks - 1) * 16;''')
-        s = rep(s, '''                    nx[q].ray = nx[q].sval ? a.samp_ray[nx[q].s] : 0;
-                }
-            }
-        });''', '''                    nx[q].ray = nx[q].sval ? a.samp_ray[nx[q].s] : 0;
-                }
-            }
-        }, NoHook{}, [&](auto f) {
-            constexpr int F = decltype(f)::value;
-            if constexpr (F >= LASTK + 3 && ((F - LASTK) & 1) == 1) {
-                constexpr int J = (F - LASTK - 3) / 2;
+        s = rep(s, '''                if constexpr (decltype(c)::value == 0) next_index();  // v_next landed at the previous boundaries
+            });''', '''                if constexpr (decltype(c)::value == 0) next_index();  // v_next landed at the previous boundaries
+            }, NoHook{}, [&](auto f) {
+                constexpr int F = decltype(f)::value;
+                if constexpr (F >= LASTK + 3 && ((F - LASTK) & 1) == 1) {
+                    constexpr int J = (F - LASTK - 3) / 2;
 #pragma unroll
-                for (int q = 0; q < NS; ++q) in3[q][J] = chain_k(q, acc2[q], inv2, std::integral_constant<int, J>{}, a.z3);
-            }
-        });
+                    for (int q = 0; q < NS; ++q) in3[q][J] = chain_k(q, acc2[q], inv2, std::integral_constant<int, J>{}, a.z3);
+                }
+            });
 #pragma unroll
-        for (int q = 0; q < NS; ++q) in3[q][7] = chain_k(q, acc2[q], inv2, std::integral_constant<int, 7>{}, a.z3);''')
+            for (int q = 0; q < NS; ++q) in3[q][7] = chain_k(q, acc2[q], inv2, std::integral_constant<int, 7>{}, a.z3);''')
         s = rep(s, '''            X3Pair in3[NS][8];
-            run_layer_ns<Net, L3, true, std::conditional_t<SAVE, VmZero, VmL3P0<NS>>, 0, 0, !SAVE>(
+            // (without block3 the record loads''', '''            // (without block3 the record loads''')
+        s = rep(s, '''            run_layer_ns<Net, L3, true, std::conditional_t<SAVE || !B3, VmZero, VmL3P0<NS>>, 0, 0, !SAVE>(
                 wb, ldsi, slot, w, lane, acc, [&](auto k) {
                     constexpr int K = decltype(k)::value;
                     X3S<NS> o;
 #pragma unroll
                     for (int q = 0; q < NS; ++q) {
-                        in3[q][K] = chain_k(q, acc2[q], inv2, k, a.z3);
-                        o.b[q] = in3[q][K];
-                    }
-                    return o;
-                }, NoHook{}, first_chunk_loads);''', '''            run_layer_ns<Net, L3, true, std::conditional_t<SAVE, VmZero, VmL3P0<NS>>, 0, 0>(
+                        if constexpr (K < 8) {''', '''            run_layer_ns<Net, L3, true, std::conditional_t<SAVE || !B3, VmZero, VmL3P0<NS>>, 0, 0, !B3>(
                 wb, ldsi, slot, w, lane, acc, [&](auto k) {
+                    constexpr int K = decltype(k)::value;
                     X3S<NS> o;
 #pragma unroll
-                    for (int q = 0; q < NS; ++q) o.b[q] = in3[q][decltype(k)::value];
-                    return o;
-                }, NoHook{}, first_chunk_loads);''')
+                    for (int q = 0; q < NS; ++q) {
+                        if constexpr (B3) {   // converted during block3.0's last k-step
+                            o.b[q] = in3[q][K];
+                        } else if constexpr (K < 8) {''')
     elif p == "v_epic":
         # the epilogue's per-lane constants (the alpha weight of unit 16 T + r, T = 0..15) read into registers
         # once per tile (4 ds_read_b128, one wait) instead of one LDS read + wait per step
